@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: camera frames/s of the BEVHeight camera->BEV forward on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,6 +11,10 @@ is reachable), inputs resident in HBM before the timed region.  One "step" = one
 (image backbone + neck + HeightNet + lift + geometry + voxel pooling + BEV head) of the per-GPU batch;
 frames shard over GPUs as independent replicas (no collective on the data path), so
 ``value`` = N * batch * K / max-over-ranks(time) and ``scaling`` is weak.
+
+A plain run does only what ``value`` needs: set-up, warm-up, the K timed steps, ``--dump-outputs DIR`` if given (the
+prediction maps of the last timed step, ``DIR/task<t>_<map>.npy``, float32; same arguments -> same inputs, so two builds
+can be compared output for output) and the line.  Every other figure below is measured only with ``--full``.
 
 Printed by rank 0 as ONE JSON line, with
 * ``value``: the K timed steps with the calibration handed over as FRESH tensor objects every frame -- the reference harness's
@@ -55,6 +59,7 @@ sys.path.insert(0, ROOT)
 MFMA_F32_PEAK_TFLOPS = 157.3    # /opt/skills/guides/MI355X_MICROARCH.md: dense f32-input MFMA peak
 MFMA_BF16_PEAK_TFLOPS = 2500.0  # same guide: dense bf16 MFMA peak (--dtype bf16 only)
 HBM_PEAK_GBPS = 8000.0
+DUMP_CAP_BYTES = 64 << 20       # --dump-outputs: at most this much in all
 
 
 def parse():
@@ -63,6 +68,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1, help="frames per GPU per step (cfg-2: 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: one frame in flight, cached / changing "
+                         "calibration, >= 1 s run, roofline passes, CPU baseline + parity against the oracle, harness eval_step, "
+                         "other_configs, train_step, native_f32_value (each can still be switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the prediction maps of the last timed step (rank 0) as DIR/<name>.npy, float32, "
+                         f"at most {DUMP_CAP_BYTES >> 20} MB in all (a fixed, seeded sample of every map above that)")
     ap.add_argument("--no-graph", action="store_true", help="eager stream launches instead of a hipGraph replay")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -102,6 +114,33 @@ def parse():
                          "use with --config cfg3 --batch 4 or --config cfg5); f32x3: float32-accurate products from three "
                          "bf16 terms per operand on the bf16 matrix cores (experimental).  Never the default.")
     return ap.parse_args()
+
+
+def dump_outputs(preds, out_dir, cap_bytes=None):
+    """Write what a caller of the timed path receives -- one single-element list per task holding a dict of NCHW maps -- as
+    ``out_dir/task<t>_<map>.npy`` (float32; non-float maps as float64).  Above ``cap_bytes`` in all, every map is replaced by the
+    same fixed, seeded sample of its flattened elements (one fraction for all maps).  Returns a record for the line."""
+    import numpy as np
+    cap_bytes = DUMP_CAP_BYTES if cap_bytes is None else cap_bytes
+    arrays = {}
+    for t, task in enumerate(preds):
+        for j, maps in enumerate(task):
+            for k, v in maps.items():
+                name = f"task{t}_{k}" if len(task) == 1 else f"task{t}_{j}_{k}"
+                v = v.detach()
+                arrays[name] = (v.float() if v.is_floating_point() else v.double()).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    frac = 1.0 if total <= cap_bytes else cap_bytes / total
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, a in arrays.items():
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += a.nbytes
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": written,
+            "sampled": None if frac == 1.0 else f"seeded sample (numpy default_rng(0)) of {frac:.4f} of every map's elements"}
 
 
 def _vp_symbol_form(sym):
@@ -224,7 +263,7 @@ def run_other_configs(args, budget_s=120.0):
             out.append({"config": cfg, "skipped": f"other_configs budget of {budget_s:.0f} s spent"})
             continue
         cmd = [sys.executable, os.path.abspath(__file__), "--sub", "--config", cfg, "--batch", str(batch), "--dtype", "bf16",
-               "--steps", str(steps), "--warmup", str(warm), "--streams", str(args.streams), "--no-plan-timing"]
+               "--steps", str(steps), "--warmup", str(warm), "--streams", str(args.streams), "--no-plan-timing", "--full"]
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=left + 30.0)
@@ -362,6 +401,14 @@ def main():
     # group, barriers, MAX over ranks, gather of the per-rank records, final barrier, one JSON line from rank 0 -- with the
     # model replaced by a sleep.  It measures nothing and says so in the line ("data": "stub").
     stub = bool(os.environ.get("SGV3D_BENCH_STUB"))
+    if stub and args.dump_outputs:
+        raise SystemExit("--dump-outputs needs the model: not with SGV3D_BENCH_STUB")
+    if args.roofline_only:
+        args.full = True            # (the instrumented pass is what that mode is for)
+    if not args.full:
+        # a plain run: set-up, warm-up, the K timed steps, --dump-outputs and the line -- nothing else
+        args.no_roofline = args.no_cpu_baseline = args.no_harness = args.no_other_configs = True
+        args.no_train_step = args.no_native_f32 = True
     if stub:
         args.no_roofline = args.no_cpu_baseline = True
     elif not torch.cuda.is_available():
@@ -450,10 +497,12 @@ def main():
     # (the plan itself is rebuilt only when the indices really changed).  A ring of distinct tensor objects with the same content.
     ring = None if stub else [{k: v.clone() for k, v in mats.items()} for _ in range(2 * nstreams + 1)]
     ctr = [0]
+    last_slot = [None]
 
     def run():
         ctr[0] += 1
-        return pipe.submit(imgs, mats if stub else ring[ctr[0] % len(ring)])
+        last_slot[0] = pipe.submit(imgs, mats if stub else ring[ctr[0] % len(ring)])
+        return last_slot[0]
     for _ in range(args.warmup * nstreams):
         run()
     if not stub:
@@ -471,12 +520,16 @@ def main():
         args.steps = max(1, args.steps)
     elapsed = timed_local(run, args.steps)          # barrier+sync | K steps | barrier+sync, MAX over ranks
     value = group.aggregate_throughput(B, args.steps, elapsed)
+    # the outputs of the last timed step, read before anything else runs on the pipeline's slots
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(pipe.result(last_slot[0], wait_host=True), args.dump_outputs)
     # calibration cache counters of the timed slots: geometry / plan kernels launched inside the timed region
     calib = {"plan_builds_before_timed_region": counters0[2],
              "plan_builds_in_timed_region": sum(c.plan.builds() for c in pipe.caches if c.plan is not None) - counters0[2],
              "geometry_launches_in_timed_region": sum(c.refreshes for c in pipe.caches) - counters0[1],
              "calibration_tensors": "fresh objects every frame (the reference harness's call pattern)"}
-    quick = args.roofline_only          # only the warm-up, the K steps above and the instrumented pass
+    quick = args.roofline_only or not args.full    # only the warm-up, the K steps above (and with --roofline-only the instrumented pass)
     single = None
     if nstreams > 1 and rank == 0 and world == 1 and not args.sub and not stub and not quick:   # same K steps with one frame in flight, for reference
         one = FramePipeline(model, imgs, mats, slots=1, use_graph=use_graph)
@@ -1189,6 +1242,7 @@ def main():
             "changing_calibration_every_frame": changing,
             "roofline": roofline, "roofline_hbm": roofline_hbm, "cpu_baseline": cpu_baseline, "parity": parity,
             "other_configs": other_configs,
+            "full": bool(args.full), "dump_outputs": dumped,
         }
     # rank 0 has been busy alone since the last collective (roofline pass, CPU baseline): every rank waits here, so that
     # no rank tears RCCL down while another one is still inside the job

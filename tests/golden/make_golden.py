@@ -33,7 +33,7 @@ from torch import nn
 
 warnings.filterwarnings("ignore")
 HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = os.environ.get("SGV3D_GOLDEN_OUT", HERE)      # tests/test_golden_regen_cpu.py regenerates into a temp dir
+OUT = os.environ.get("SGV3D_GOLDEN_OUT", HERE)      # regenerate elsewhere to compare with the committed files
 REF = "/root/reference"
 f32 = np.float32
 

@@ -205,7 +205,7 @@ def main(out_dir=None):
 
     def seeded(ctor, *a, **k):
         """Constructors draw their initial weights from the GLOBAL generator: reseed it per construction site, so the
-        fixture regenerates bit for bit (tests/test_golden_regen_cpu.py)."""
+        fixture regenerates bit for bit."""
         site[0] += 1
         torch.manual_seed(20261007 + 1000 * site[0])
         return ctor(*a, **k)

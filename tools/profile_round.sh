@@ -23,7 +23,7 @@ cd /tmp
 echo "[profile_round] $(date +%H:%M:%S) 2. kernel trace + stats of the same command (no CPU baseli" | tee -a $KEEP/progress.log
 #    per-kernel durations are those of the kernels alone (with 3 frames in flight concurrent kernels stretch each
 #    other) and compare directly with roofline.avg_launch_us of the bench line, which is measured the same way.
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o ${TAG}_bench -- python3 $R/bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-plan-timing --no-other-configs --no-harness --no-train-step --no-native-f32 --streams 1 > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o ${TAG}_bench -- python3 $R/bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-plan-timing --no-other-configs --no-harness --no-train-step --no-native-f32 --streams 1 > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/rocprof.err
 # 2r. the ROOFLINE population alone: bench.py --roofline-only = warm-up + the instrumented pass, one stream, eager launches from the
 #     first to the last forward -- the per-symbol averages of this trace are over exactly the launches roofline.frac is made of
 #     (bench.py pairs its own flops per launch with this file: roofline.frac_from_rocprof)
@@ -32,7 +32,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o ${TAG}_bench_roo
 # 2b. the HEADLINE command itself (three frames in flight) under the kernel trace: concurrent kernels stretch each other,
 echo "[profile_round] $(date +%H:%M:%S) 2b. the HEADLINE command itself (three frames in flight) u" | tee -a $KEEP/progress.log
 #     so these per-kernel durations are "under load" figures, not comparable with roofline.avg_launch_us
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o ${TAG}_bench_3inflight -- python3 $R/bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-roofline --no-other-configs --no-harness > $OUT/${TAG}_bench_3inflight_under_rocprof.json 2> $OUT/rocprof3.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o ${TAG}_bench_3inflight -- python3 $R/bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-roofline --no-other-configs --no-harness > $OUT/${TAG}_bench_3inflight_under_rocprof.json 2> $OUT/rocprof3.err
 # 2c. per-layer table (HIP events, one frame at a time) with the tiles chosen for three frames in flight, and for one
 echo "[profile_round] $(date +%H:%M:%S) 2c. per-layer table (HIP events, one frame at a time) with" | tee -a $KEEP/progress.log
 SGV3D_TUNE_STREAMS=3 python3 $R/tools/layer_report.py > $OUT/${TAG}_layers_cfg2_tiles_for_3inflight.txt 2> $OUT/layers3.err
@@ -42,11 +42,11 @@ echo "[profile_round] $(date +%H:%M:%S) 2d. the three launches of the F(4x4) Win
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o ${TAG}_wino4 -- python3 $R/tools/wino4_trace.py > /dev/null 2> $OUT/wino4.err
 # 3. HBM traffic counters, separate passes (FETCH_SIZE and WRITE_SIZE do not fit one pass)
 echo "[profile_round] $(date +%H:%M:%S) 3. HBM traffic counters, separate passes (FETCH_SIZE and W" | tee -a $KEEP/progress.log
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT -o ${TAG}_pmc_fetch -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-other-configs --no-harness > /dev/null 2> $OUT/pmc_fetch.err
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT -o ${TAG}_pmc_write -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-other-configs --no-harness > /dev/null 2> $OUT/pmc_write.err
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT -o ${TAG}_pmc_fetch -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-other-configs --no-harness > /dev/null 2> $OUT/pmc_fetch.err
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT -o ${TAG}_pmc_write -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-other-configs --no-harness > /dev/null 2> $OUT/pmc_write.err
 # 3b. MFMA utilisation counters (own pass; SQ counters fit one pass)
 echo "[profile_round] $(date +%H:%M:%S) 3b. MFMA utilisation counters (own pass; SQ counters fit o" | tee -a $KEEP/progress.log
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT -o ${TAG}_pmc_mfma -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-other-configs --no-harness --streams 1 > /dev/null 2> $OUT/pmc_mfma.err
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_BUSY_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT -o ${TAG}_pmc_mfma -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-roofline --no-other-configs --no-harness --streams 1 > /dev/null 2> $OUT/pmc_mfma.err
 fi
 if [[ $PARTS == *c* ]]; then
 # 7. the bf16 configurations: one frame in flight under the kernel trace (cfg-3 batch 4, cfg-5 batch 1), and their per-layer tables
@@ -83,6 +83,6 @@ if [[ $PARTS == *a* ]]; then
 #    from the SAME tree's traces
 cp $KEEP/${TAG}_bench_roofline_kernel_stats.csv $KEEP/${TAG}_bench_roofline_under_rocprof.json $KEEP/${TAG}_hbm_traffic.json $R/profiles/
 echo "[profile_round] $(date +%H:%M:%S) 1. the bench line itself (with the CPU baseline)" | tee -a $KEEP/progress.log
-python3 $R/bench.py --steps 20 --warmup 3 > $KEEP/${TAG}_bench.json 2> $KEEP/bench.err
+python3 $R/bench.py --full --steps 20 --warmup 3 > $KEEP/${TAG}_bench.json 2> $KEEP/bench.err
 fi
 ls -la $KEEP
