@@ -1000,6 +1000,34 @@ int sgv3d_deform_im2col3x3_backward(int batch, int h, int w, int channels, int g
                                     const float *offset, int off_ld, const float *grad_col, float *grad_x,
                                     float *grad_offset, int grad_off_ld, void *stream);
 
+/* ================================================================================================
+ * Image preprocessing (csrc/preprocess.hip): decoded uint8 camera frames -> model input
+ * ================================================================================================ */
+
+/* HOST function (host pointers, no GPU work): Pillow's bicubic resampling coefficients for one axis, in_size -> out_size
+ * (src/libImaging/Resample.c precompute_coeffs + normalize_coeffs_8bpc: 22 fractional bits, rounded away from zero).
+ *   bounds i32 [out_size][2] = (first input pixel, number of taps); coeffs i32 [out_size][*ksize], zero past the taps.
+ * With bounds or coeffs NULL only *ksize is written.  A downscale above 4x (ksize > 17) is rejected. */
+int sgv3d_resample_coeffs(int in_size, int out_size, int32_t *bounds, int32_t *coeffs, int *ksize);
+
+/* img_transform + mmcv.imnormalize + HWC->CHW of the reference's dataset (dataset/nusc_mv_det_dataset.py:133-161,
+ * 594-625) for eval-time settings, one launch for a batch of frames:
+ *   src u8 [frames, in_h, in_w, 3] -> Pillow bicubic resize to rs_h x rs_w (two integer passes, bit-exact), crop of the
+ *   out_h x out_w box at (crop_x, crop_y) of the resized image (outside it: 0, as PIL's crop), optional left-right flip,
+ *   optional R<->B swap (to_rgb), y = f32(f32(x - mean[c]) * f32(1 / (double)std[c])) -> dst f32 [frames, 3, out_h, out_w].
+ *   x/y bounds and coefficients: device copies of sgv3d_resample_coeffs(in_w, rs_w) / (in_h, rs_h); mean / std: HOST
+ *   float[3] in output channel order. */
+int sgv3d_preprocess_images(int frames, int in_h, int in_w, int rs_h, int rs_w, int crop_x, int crop_y, int out_h,
+                            int out_w, int flip, int swap_rb, const int32_t *xbounds, const int32_t *xcoeffs, int xksize,
+                            const int32_t *ybounds, const int32_t *ycoeffs, int yksize, const float *mean,
+                            const float *std, const uint8_t *src, float *dst, void *stream);
+/* The SGV3D semantic mask through the same transform (dataset/...:603-614): channel 0 of src u8 [frames, in_h, in_w,
+ * channels] resized, cropped and flipped as above -> dst u8 [frames, out_h, out_w] = value / 40 (integer division). */
+int sgv3d_preprocess_mask(int frames, int in_h, int in_w, int channels, int rs_h, int rs_w, int crop_x, int crop_y,
+                          int out_h, int out_w, int flip, const int32_t *xbounds, const int32_t *xcoeffs, int xksize,
+                          const int32_t *ybounds, const int32_t *ycoeffs, int yksize, const uint8_t *src, uint8_t *dst,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -186,6 +186,10 @@ _PROTOS = {
     "sgv3d_deform_im2col3x3_backward": (c_int, [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "sgv3d_rotate_iou_pairs": (c_int, [c_int, c_int] + [c_void_p] * 6 + [c_int, c_int, c_void_p, c_void_p]),
     "sgv3d_kitti_eval_curves": (c_int, [c_int] + [c_void_p] * 9 + [c_int, ctypes.c_double, c_int, c_ll, c_int] + [c_void_p] * 4),
+    "sgv3d_resample_coeffs": (c_int, [c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int)]),
+    "sgv3d_preprocess_images": (c_int, [c_int] * 11 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int] +
+                                [ctypes.POINTER(ctypes.c_float)] * 2 + [c_void_p] * 3),
+    "sgv3d_preprocess_mask": (c_int, [c_int] * 11 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 3),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

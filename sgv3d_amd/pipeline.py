@@ -223,16 +223,26 @@ class GraphedForward:
 
 
 class FramePipeline:
-    def __init__(self, model, imgs, mats, slots=2, use_graph=True, strict=False):
+    def __init__(self, model, imgs, mats, slots=2, use_graph=True, strict=False, preprocess=None):
         assert imgs.is_cuda, "FramePipeline runs on the GPU"
         self.model = model
+        # preprocess (an ImagePreprocessor): `imgs` and every submitted frame are uint8 camera frames; each slot's static input is a
+        # uint8 frame buffer and the preprocessing launch is the first node of the slot's graph
+        self.preprocess = preprocess
         self.capture_error = None                  # the exception that made the pipeline fall back to eager launches
         self.device = imgs.device
         self.slots = max(1, int(slots))
         self.streams = []
         for _ in range(self.slots):                # pairwise distinct HIP streams (hip_ops.distinct_stream)
             self.streams.append(hip_ops.distinct_stream(imgs.device, self.streams))
-        self.in_imgs = [static_copy(imgs) for _ in range(self.slots)]
+        if preprocess is None:
+            self.in_frames = None
+            self.in_imgs = [static_copy(imgs) for _ in range(self.slots)]
+        else:
+            self.in_frames = [static_copy(imgs) for _ in range(self.slots)]
+            with torch.no_grad():
+                self.in_imgs = [preprocess(f)[0] for f in self.in_frames]
+            imgs = self.in_imgs[0]
         self.in_mats = [{k: static_copy(v) for k, v in mats.items()} for _ in range(self.slots)]
         self.caches = [CalibrationCache() for _ in range(self.slots)]
         self._last_mats = [None] * self.slots      # [(tensor, version)] of the mats last copied into the slot
@@ -255,11 +265,11 @@ class FramePipeline:
                         g = torch.cuda.CUDAGraph()
                         s.wait_stream(torch.cuda.current_stream(imgs.device))
                         with torch.cuda.stream(s), self._slot(i):
-                            model(self.in_imgs[i], self.in_mats[i])      # builds the slot's geometry + plan, eagerly
+                            self._forward(i)                             # builds the slot's geometry + plan, eagerly
                             torch.cuda.synchronize(imgs.device)
                             # (outside inference mode, see capture_begin; the forward's tensors are then ordinary ones)
                             with torch.inference_mode(False), torch.no_grad(), torch.cuda.graph(g, stream=s):
-                                self.outputs[i] = model(self.in_imgs[i], self.in_mats[i])
+                                self.outputs[i] = self._forward(i)
                         torch.cuda.current_stream(imgs.device).wait_stream(s)
                         self.graphs.append(g)
                 except CAPTURE_ERRORS as e:
@@ -291,6 +301,12 @@ class FramePipeline:
             self.pipe.model.backbone.calib_cache = self.pipe._own_cache
             return False
 
+    def _forward(self, i):
+        """Slot i's forward on its static inputs (preceded by the preprocessing launch into its float image buffer)."""
+        if self.preprocess is not None:
+            self.preprocess(self.in_frames[i], out=self.in_imgs[i])
+        return self.model(self.in_imgs[i], self.in_mats[i])
+
     def _slot(self, i):
         """The model's backbone uses slot i's calibration cache inside this context."""
         return FramePipeline._Slot(self, i)
@@ -304,7 +320,7 @@ class FramePipeline:
                 self.graphs[i].replay()
             else:
                 with self._slot(i), eager_forward(self.model):
-                    self.outputs[i] = self.model(self.in_imgs[i], self.in_mats[i])
+                    self.outputs[i] = self._forward(i)
             self.done[i].record()
         return i
 
@@ -315,14 +331,15 @@ class FramePipeline:
         return all(k in last and last[k][0] is v and last[k][1] is not None and last[k][1] == tensor_version(v) for k, v in mats.items())
 
     def submit(self, imgs, mats):
-        """Copy a frame into the next slot's static inputs (on that slot's stream) and run it."""
+        """Copy a frame into the next slot's static inputs (on that slot's stream) and run it.  With ``preprocess``, ``imgs``
+        are the uint8 camera frames."""
         i = self._next
         s = self.streams[i]
         # the frame may have been produced on the caller's stream (a preprocessing kernel, a non_blocking H2D copy),
         # and kernels reading this slot's previous outputs may still be queued there
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s), torch.no_grad():
-            self.in_imgs[i].copy_(imgs, non_blocking=True)
+            (self.in_imgs if self.in_frames is None else self.in_frames)[i].copy_(imgs, non_blocking=True)
             if imgs.is_cuda:
                 imgs.record_stream(s)
             if not self._same_mats(i, mats):
