@@ -1028,6 +1028,59 @@ int sgv3d_preprocess_mask(int frames, int in_h, int in_w, int channels, int rs_h
                           const int32_t *ybounds, const int32_t *ycoeffs, int yksize, const uint8_t *src, uint8_t *dst,
                           void *stream);
 
+/* ================================================================================================
+ * Training-time camera augmentation (csrc/augment.hip): the reference dataset's is_train image path
+ * ================================================================================================ */
+
+#define SGV3D_FILTER_BICUBIC 0
+#define SGV3D_FILTER_LANCZOS 1
+
+/* HOST function: sgv3d_resample_coeffs for Pillow's BICUBIC (a = -0.5, support 2) or LANCZOS (sinc(x) sinc(x / 3) on
+ * [-3, 3)) filter, any downscale (ksize = 2 ceil(support max(in / out, 1)) + 1).  With bounds or coeffs NULL only *ksize
+ * is written. */
+int sgv3d_resample_coeffs_filter(int filter, int in_size, int out_size, int32_t *bounds, int32_t *coeffs, int *ksize);
+
+/* One frame of an augmentation batch (112 bytes). */
+typedef struct sgv3d_aug_frame {
+    int32_t ie;           /* 1: intrinsic / extrinsic rectification (Lanczos resize, paste / crop, rotate) */
+    int32_t bright;       /* 1: brightness jitter (images only) */
+    int32_t rs_w, rs_h;   /* Lanczos-resized size, int(W ratio) x int(H ratio), >= 1 */
+    int32_t off_x, off_y; /* canvas (y, x) = resized (y + off_y, x + off_x), 0 outside: paste (-w_min, -h_min) or crop */
+    int32_t kx, ky;       /* Lanczos ksize of each axis */
+    int64_t xtab, ytab;   /* int32 offsets into tables: bounds [rs][2] followed by coeffs [rs][k] */
+    int32_t slot;         /* index among the batch's rectified frames, in frame order */
+    int32_t pad;
+    double affine[6];     /* Image.rotate's inverse map: x_src = a0 (x + .5) + a1 (y + .5) + a2, y_src = a3 .. a5 */
+    double u;             /* the brightness draw: beta = u (100 - mean gray), |beta| <= 50 */
+} sgv3d_aug_frame;
+
+/* HOST function: workspace bytes of sgv3d_augment_images (mask = 0) / sgv3d_augment_mask (mask = 1) for `frames`
+ * frames of which `rectified` have ie set; 0 for bad arguments. */
+size_t sgv3d_augment_workspace_bytes(int frames, int rectified, int in_h, int in_w, int out_h, int out_w, int mask);
+
+/* get_image's training path for a batch (dataset/nusc_mv_det_dataset.py:550-554, 594-625):
+ *   src u8 [frames, in_h, in_w, 3] -> rectified frames: Lanczos resize / paste or crop / bicubic rotate -> Pillow
+ *   bicubic resize to rs_h x rs_w + crop (as sgv3d_preprocess_images, no flip) -> jittered frames: cv2.convertScaleAbs
+ *   brightness -> mmcv.imnormalize -> dst f32 [frames, 3, out_h, out_w].  Every step bit-exact to the 8-bit libraries.
+ *   frames_host / frames_dev: the same descriptors in host memory (validated here) and device memory (read by the
+ *   kernels); tables: device int32 [tables_len] Lanczos tables (sgv3d_resample_coeffs_filter); x/y bounds and coeffs:
+ *   device copies of sgv3d_resample_coeffs(in_w, rs_w) / (in_h, rs_h); mean / std: HOST float[3]; work: device,
+ *   8-byte aligned, sgv3d_augment_workspace_bytes long.  Six launches whatever the batch; three when nothing is
+ *   rectified. */
+int sgv3d_augment_images(int frames, int in_h, int in_w, const sgv3d_aug_frame *frames_host,
+                         const sgv3d_aug_frame *frames_dev, const int32_t *tables, long long tables_len, int rs_h,
+                         int rs_w, int crop_x, int crop_y, int out_h, int out_w, int swap_rb, const int32_t *xbounds,
+                         const int32_t *xcoeffs, int xksize, const int32_t *ybounds, const int32_t *ycoeffs, int yksize,
+                         const float *mean, const float *std, const uint8_t *src, void *work, size_t work_bytes,
+                         float *dst, void *stream);
+/* The semantic mask through the same rectification and resize + crop (:553-554, :603-614): channel 0 of src u8
+ * [frames, in_h, in_w, channels] -> dst u8 [frames, out_h, out_w] = value / 40.  bright must be 0. */
+int sgv3d_augment_mask(int frames, int in_h, int in_w, int channels, const sgv3d_aug_frame *frames_host,
+                       const sgv3d_aug_frame *frames_dev, const int32_t *tables, long long tables_len, int rs_h,
+                       int rs_w, int crop_x, int crop_y, int out_h, int out_w, const int32_t *xbounds,
+                       const int32_t *xcoeffs, int xksize, const int32_t *ybounds, const int32_t *ycoeffs, int yksize,
+                       const uint8_t *src, void *work, size_t work_bytes, uint8_t *dst, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -190,6 +190,14 @@ _PROTOS = {
     "sgv3d_preprocess_images": (c_int, [c_int] * 11 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int] +
                                 [ctypes.POINTER(ctypes.c_float)] * 2 + [c_void_p] * 3),
     "sgv3d_preprocess_mask": (c_int, [c_int] * 11 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 3),
+    "sgv3d_resample_coeffs_filter": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int)]),
+    "sgv3d_augment_workspace_bytes": (c_size_t, [c_int] * 7),
+    "sgv3d_augment_images": (c_int, [c_int] * 3 + [c_void_p] * 3 + [c_ll] + [c_int] * 7 +
+                             [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int] + [ctypes.POINTER(ctypes.c_float)] * 2 +
+                             [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "sgv3d_augment_mask": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_ll] + [c_int] * 6 +
+                           [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int] +
+                           [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
