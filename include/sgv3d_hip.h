@@ -1081,6 +1081,61 @@ int sgv3d_augment_mask(int frames, int in_h, int in_w, int channels, const sgv3d
                        const int32_t *xcoeffs, int xksize, const int32_t *ybounds, const int32_t *ycoeffs, int yksize,
                        const uint8_t *src, void *work, size_t work_bytes, uint8_t *dst, void *stream);
 
+/* ================================================================================================
+ * JPEG decoding (csrc/jpeg.hip): camera files -> the uint8 RGB frames Pillow's Image.open + np.asarray give
+ * ================================================================================================ */
+
+/* One Huffman table in the form the kernels read (1424 bytes): libjpeg's jpeg_make_d_derived_tbl. */
+typedef struct sgv3d_jpeg_huff {
+    uint16_t look[512];   /* next 9 bits -> (code length << 8) | symbol; 0: the code is longer than 9 bits */
+    int32_t maxcode[18];  /* largest code of each length 1..16, -1 if none; [17] a sentinel above every code */
+    int32_t valoff[18];   /* symbol of code c of length l = huffval[c + valoff[l]] */
+    uint8_t huffval[256];
+} sgv3d_jpeg_huff;
+
+/* One frame of a decode batch (8976 bytes), filled by sgv3d_jpeg_parse. */
+typedef struct sgv3d_jpeg_frame {
+    int32_t width, height;
+    int32_t hs, vs;             /* luma sampling factors (1, 1), (2, 1) or (2, 2); chroma 1 x 1 */
+    int32_t mcux, mcuy;         /* MCU grid: ceil(width / 8 hs) x ceil(height / 8 vs) */
+    int32_t blocks_per_mcu;     /* hs vs + 2, in decode order: the luma blocks row by row, Cb, Cr */
+    int32_t restart;            /* restart interval in MCUs, 0: none */
+    int64_t scan_off;           /* byte offset of the entropy-coded segment: in the file (parse), in `data` (decode) */
+    int32_t scan_len;           /* its length in bytes, up to (not including) the EOI marker */
+    int32_t pad;
+    uint16_t quant[3][64];      /* each component's quantisation table in natural order */
+    sgv3d_jpeg_huff huff[3][2]; /* each component's [0] DC and [1] AC table */
+} sgv3d_jpeg_frame;
+
+/* Per-frame status bits that sgv3d_jpeg_decode leaves in `status` (0: the frame decoded cleanly). */
+#define SGV3D_JPEG_EBADCODE 1   /* a bit pattern that is no code of its Huffman table */
+#define SGV3D_JPEG_ECOEF 2      /* a run that takes the coefficient index past 63 */
+#define SGV3D_JPEG_ESHORT 4     /* the scan ended before the last MCU (or a code ran into a marker) */
+#define SGV3D_JPEG_EMARKER 8    /* a marker where no restart interval ends */
+#define SGV3D_JPEG_ELONG 16     /* more blocks than the frame has */
+
+/* HOST function: parse one JPEG file (host bytes) into *desc (scan_off relative to `data`) and its size.  Accepts
+ * Huffman-coded sequential 8-bit frames (SOF0 / SOF1) with three YCbCr components in one interleaved scan, luma
+ * sampling 1x1 / 2x1 / 2x2 and chroma 1x1, with or without restart markers; anything else is rejected with a message
+ * that names the feature. */
+int sgv3d_jpeg_parse(const uint8_t *data, size_t len, sgv3d_jpeg_frame *desc, int *h, int *w);
+
+/* HOST function: workspace bytes of sgv3d_jpeg_decode for `frames` frames of h x w, scans of up to max_bytes bytes and
+ * subsequences of seq_bytes bytes; 0 for bad arguments. */
+size_t sgv3d_jpeg_workspace_bytes(int frames, int h, int w, int max_bytes, int seq_bytes);
+
+/* Decode a batch of parsed frames -> dst u8 [frames, h, w, 3] (RGB), byte for byte libjpeg-turbo's default decode
+ * (ISLOW IDCT, fancy upsampling, jdcolor's fixed-point YCbCr -> RGB).  frames_host / frames_dev: the same descriptors
+ * in host memory (validated here) and device memory (read by the kernels), every frame h x w with the same sampling and
+ * scan_len <= max_bytes; data: device bytes holding each frame's scan at its scan_off (a multiple of 16, with the scan
+ * rounded up to 16 bytes inside data_len); status: device int32 [frames], written with the SGV3D_JPEG_E* bits of each
+ * frame; work: device, 16-byte aligned, sgv3d_jpeg_workspace_bytes long.  The entropy decode splits every scan into
+ * seq_bytes subsequences (8 <= seq_bytes <= 2^20) decoded in parallel and resolved exactly by self-synchronisation.
+ * Eight launches whatever the batch and the data; grids follow max_bytes and h x w, not the actual lengths. */
+int sgv3d_jpeg_decode(int frames, int h, int w, int max_bytes, int seq_bytes, const sgv3d_jpeg_frame *frames_host,
+                      const sgv3d_jpeg_frame *frames_dev, const uint8_t *data, long long data_len, int32_t *status,
+                      void *work, size_t work_bytes, uint8_t *dst, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,9 @@ _PROTOS = {
     "sgv3d_augment_mask": (c_int, [c_int] * 4 + [c_void_p] * 3 + [c_ll] + [c_int] * 6 +
                            [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int] +
                            [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "sgv3d_jpeg_parse": (c_int, [c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "sgv3d_jpeg_workspace_bytes": (c_size_t, [c_int] * 5),
+    "sgv3d_jpeg_decode": (c_int, [c_int] * 5 + [c_void_p] * 3 + [c_ll] + [c_void_p] * 2 + [c_size_t] + [c_void_p] * 2),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

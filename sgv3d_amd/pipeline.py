@@ -223,19 +223,37 @@ class GraphedForward:
 
 
 class FramePipeline:
-    def __init__(self, model, imgs, mats, slots=2, use_graph=True, strict=False, preprocess=None):
-        assert imgs.is_cuda, "FramePipeline runs on the GPU"
+    def __init__(self, model, imgs, mats, slots=2, use_graph=True, strict=False, preprocess=None, decode=None):
+        if decode is not None and preprocess is None:
+            raise ValueError("FramePipeline: decode= needs preprocess= (the decoded frames are uint8)")
+        assert decode is not None or imgs.is_cuda, "FramePipeline runs on the GPU"
         self.model = model
         # preprocess (an ImagePreprocessor): `imgs` and every submitted frame are uint8 camera frames; each slot's static input is a
         # uint8 frame buffer and the preprocessing launch is the first node of the slot's graph
         self.preprocess = preprocess
+        # decode (a JpegDecoder): `imgs` and every submitted frame are B*S*N encoded files (bytes-like, in [B, S, N] order);
+        # each slot has its own pinned staging buffer, device staging and workspace (jpeg.JpegStaging), and the upload and the
+        # decode launches are the first nodes of the slot's graph, in front of the preprocessing launch
+        self.decode = decode
+        self.stagings = None
         self.capture_error = None                  # the exception that made the pipeline fall back to eager launches
-        self.device = imgs.device
+        self.device = decode.device if decode is not None else imgs.device
         self.slots = max(1, int(slots))
         self.streams = []
         for _ in range(self.slots):                # pairwise distinct HIP streams (hip_ops.distinct_stream)
-            self.streams.append(hip_ops.distinct_stream(imgs.device, self.streams))
-        if preprocess is None:
+            self.streams.append(hip_ops.distinct_stream(self.device, self.streams))
+        if decode is not None:
+            from .jpeg import JpegStaging
+            self.stagings = [JpegStaging(decode, tuple(mats['sensor2ego_mats'].shape[:3])) for _ in range(self.slots)]
+            with torch.no_grad():
+                for st in self.stagings:
+                    st.stage(imgs)
+                    st.launch()
+            self.in_frames = [st.out for st in self.stagings]
+            with torch.no_grad():
+                self.in_imgs = [preprocess(f)[0] for f in self.in_frames]
+            imgs = self.in_imgs[0]
+        elif preprocess is None:
             self.in_frames = None
             self.in_imgs = [static_copy(imgs) for _ in range(self.slots)]
         else:
@@ -302,7 +320,10 @@ class FramePipeline:
             return False
 
     def _forward(self, i):
-        """Slot i's forward on its static inputs (preceded by the preprocessing launch into its float image buffer)."""
+        """Slot i's forward on its static inputs (preceded by the upload + decode launches into its uint8 frame buffer and
+        the preprocessing launch into its float image buffer)."""
+        if self.stagings is not None:
+            self.stagings[i].launch()
         if self.preprocess is not None:
             self.preprocess(self.in_frames[i], out=self.in_imgs[i])
         return self.model(self.in_imgs[i], self.in_mats[i])
@@ -332,16 +353,22 @@ class FramePipeline:
 
     def submit(self, imgs, mats):
         """Copy a frame into the next slot's static inputs (on that slot's stream) and run it.  With ``preprocess``, ``imgs``
-        are the uint8 camera frames."""
+        are the uint8 camera frames; with ``decode``, the B*S*N encoded files, parsed and packed into the slot's pinned
+        staging buffer once the slot's previous frame (whose upload reads that buffer) is done -- a wait for that frame
+        only, not for the device."""
         i = self._next
         s = self.streams[i]
+        if self.stagings is not None:
+            self.done[i].synchronize()
+            self.stagings[i].stage(imgs)
         # the frame may have been produced on the caller's stream (a preprocessing kernel, a non_blocking H2D copy),
         # and kernels reading this slot's previous outputs may still be queued there
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s), torch.no_grad():
-            (self.in_imgs if self.in_frames is None else self.in_frames)[i].copy_(imgs, non_blocking=True)
-            if imgs.is_cuda:
-                imgs.record_stream(s)
+            if self.stagings is None:
+                (self.in_imgs if self.in_frames is None else self.in_frames)[i].copy_(imgs, non_blocking=True)
+                if imgs.is_cuda:
+                    imgs.record_stream(s)
             if not self._same_mats(i, mats):
                 keys = list(mats)
                 torch._foreach_copy_([self.in_mats[i][k] for k in keys], [mats[k] for k in keys], non_blocking=True)   # one launch
