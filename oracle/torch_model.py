@@ -103,10 +103,10 @@ def secondfpn(sd, p, feats, cfg):
     return torch.cat(ups, 1)
 
 
-def deform_conv3x3(x, offset, weight, groups):
-    """mmcv 1.4.0 DeformConv2dPack semantics (DCNv1, deform_groups=1, stride 1, pad 1, dil 1):
-    offset channel 2t = dy, 2t+1 = dx of tap t (row-major); bilinear sampling with zero padding,
-    samples outside (-1, H) x (-1, W) are zero; grouped 3x3 weights, no bias."""
+def deform_im2col3x3(x, offset):
+    """The deformable bilinear im2col of mmcv 1.4.0 DeformConv2dPack (DCNv1, deform_groups=1, stride 1, pad 1, dil 1):
+    offset channel 2t = dy, 2t+1 = dx of tap t (row-major); bilinear sampling with zero padding, samples outside
+    (-1, H) x (-1, W) are zero.  -> col [B, C, 9, H, W], differentiable in x and offset."""
     B, C, H, W = x.shape
     ys, xs = torch.meshgrid(torch.arange(H, dtype=x.dtype, device=x.device), torch.arange(W, dtype=x.dtype, device=x.device),
                             indexing="ij")
@@ -126,7 +126,13 @@ def deform_conv3x3(x, offset, weight, groups):
             idx = (hh.clamp(0, H - 1) * W + ww.clamp(0, W - 1))[:, None].expand(B, C, H, W).reshape(B, C, -1)
             val = val + torch.gather(flat, 2, idx).reshape(B, C, H, W) * (wt * ok)[:, None]
         cols.append(val)
-    col = torch.stack(cols, 2)                                           # [B, C, 9, H, W]
+    return torch.stack(cols, 2)                                          # [B, C, 9, H, W]
+
+
+def deform_conv3x3(x, offset, weight, groups):
+    """mmcv 1.4.0 DeformConv2dPack semantics: ``deform_im2col3x3`` followed by the grouped 3x3 weights, no bias."""
+    B, C, H, W = x.shape
+    col = deform_im2col3x3(x, offset)                                    # [B, C, 9, H, W]
     cout = weight.shape[0]
     cpg, opg = C // groups, cout // groups
     out = x.new_zeros(B, cout, H, W)

@@ -8,6 +8,9 @@ namespace {
 
 constexpr int kBlock = 256;
 
+// max that propagates NaN like torch's pooling kernels (`val > max || isnan(val)`); fmaxf would drop it
+__device__ __forceinline__ float max_nan(float m, float v) { return (v > m || v != v) ? v : m; }
+
 // nn.MaxPool2d(3, stride 2, pad 1) of the mmdet ResNet stem (built at layers/backbones/lss_fpn.py:296)
 __global__ __launch_bounds__(kBlock) void maxpool3x3s2_kernel(int B, int H, int W, int C4, int OH, int OW,
                                                               const float4 *__restrict__ x, float4 *__restrict__ y) {
@@ -30,7 +33,7 @@ __global__ __launch_bounds__(kBlock) void maxpool3x3s2_kernel(int B, int H, int 
             const int iw = ow * 2 - 1 + dx;
             if ((unsigned)iw >= (unsigned)W) continue;
             const float4 v = x[((long long)(b * H + ih) * W + iw) * C4 + c];
-            m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+            m.x = max_nan(m.x, v.x); m.y = max_nan(m.y, v.y); m.z = max_nan(m.z, v.z); m.w = max_nan(m.w, v.w);
         }
     }
     y[i] = m;
@@ -62,7 +65,7 @@ __global__ __launch_bounds__(kBlock) void maxpool3x3s2_bf16_kernel(int B, int H,
             if ((unsigned)iw >= (unsigned)W) continue;
             const mp_bf16x8 v = x[((long long)(b * H + ih) * W + iw) * C8 + c];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) m[j] = fmaxf(m[j], (float)v[j]);
+            for (int j = 0; j < 8; ++j) m[j] = max_nan(m[j], (float)v[j]);
         }
     }
     mp_bf16x8 o;

@@ -598,6 +598,15 @@ def test_bf16_maxpool(bf16_mode):
     y = hip_ops.maxpool3x3s2(x.permute(0, 2, 3, 1).contiguous().to(DEV))
     want = F.max_pool2d(x.float(), 3, 2, 1)
     assert y.dtype == torch.bfloat16 and torch.equal(y.float().permute(0, 3, 1, 2).cpu(), want)
+    # NaN propagates as in F.max_pool2d: one NaN, a window of NaNs only, an all -inf window
+    x[:, 0, 3, 5] = float("nan")
+    x[:, 1, :2, :2] = float("nan")
+    x[:, 2, :2, :2] = float("-inf")
+    x[:, 4, 7, 8:10] = float("nan")
+    y = hip_ops.maxpool3x3s2(x.permute(0, 2, 3, 1).contiguous().to(DEV)).float().permute(0, 3, 1, 2).cpu()
+    want = F.max_pool2d(x.float(), 3, 2, 1)
+    assert bool(want.isnan().any()) and bool(want.isneginf().any())
+    assert torch.equal(y.isnan(), want.isnan()) and torch.equal(torch.nan_to_num(y, nan=0.0), torch.nan_to_num(want, nan=0.0))
 
 
 @pytest.mark.parametrize("cin,cout,ks,H,W,x_bf16", [(64, 32, 2, 9, 11, True), (160, 64, 4, 6, 7, True), (80, 64, 1, 10, 12, False),

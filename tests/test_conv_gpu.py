@@ -1,6 +1,8 @@
 """GPU: MFMA implicit-GEMM convolution family and the small layers against plain PyTorch fp32 on CPU
 (F.conv2d / F.conv_transpose2d / F.max_pool2d ...: the fp32 reference of a floating-point kernel).
 Tolerance: 1e-3 (BASELINE north_star, fp32)."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -195,11 +197,30 @@ def test_conv_rejects_bad_args(hip):
 
 
 # ------------------------------------------------------------------------------------------ small layers
+def _nan_windows(x):
+    """NaN propagates as in F.max_pool2d: one NaN in a window, a window of NaNs only, an all -inf window, -inf beside values."""
+    x[:, 0, 3, 5] = math.nan                           # one NaN in windows (1, 2) and (1, 3)
+    x[:, 1, :2, :2] = math.nan                         # window (0, 0) of channel 1 holds NaN only
+    x[:, 2, :2, :2] = -math.inf                        # window (0, 0) of channel 2 is all -inf
+    x[:, 3, 4, 6] = -math.inf
+    x[:, 4, 7, 8:10] = math.nan                        # two NaNs in one window
+    return x
+
+
+def _equal_nan(a, b):
+    return torch.equal(a.isnan(), b.isnan()) and torch.equal(torch.nan_to_num(a, nan=0.0), torch.nan_to_num(b, nan=0.0))
+
+
 def test_maxpool(hip):
     from sgv3d_amd.hip_ops import maxpool3x3s2
     x = torch.randn(2, 64, 11, 14)
     y = maxpool3x3s2(nhwc(x).to(DEV))
     assert torch.equal(nchw(y.cpu()), F.max_pool2d(x, 3, 2, 1))
+    x = _nan_windows(x)
+    y = nchw(maxpool3x3s2(nhwc(x).to(DEV)).cpu())
+    want = F.max_pool2d(x, 3, 2, 1)
+    assert bool(want.isnan().any()) and bool(want.isneginf().any())
+    assert _equal_nan(y, want)
 
 
 def test_layout_kernels(hip):

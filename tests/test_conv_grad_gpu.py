@@ -256,6 +256,56 @@ def test_transposed_conv_weight_gradient_by_role_swap():
     assert float((dw.cpu().double() - wr.grad).abs().max()) <= 2e-5 * float(wr.grad.abs().max())
 
 
+@pytest.mark.parametrize("cin,k,cout", [
+    (1024, 1, 128), (2048, 2, 128),                          # cfg-2 image neck
+    (80, 1, 64), (160, 2, 64), (320, 4, 64), (640, 8, 64),   # BEV neck
+    (87, 1, 64), (174, 2, 64), (348, 4, 64), (696, 8, 64),   # cfg-5 BEV neck: 87 / 174 channels go through _pad4
+])
+def test_conv_transpose2d_autograd(cin, k, cout):
+    """conv_grad.conv_transpose2d (the SECONDFPN deblocks, kernel == stride) through its autograd function: forward, dx and
+    dw against float64 F.conv_transpose2d autograd at the real channel counts.  Input channel counts that are not multiples
+    of 4 reach the zero padding of the input and the channel fix-up of dx."""
+    g = torch.Generator().manual_seed(cin + k)
+    B, H, W = 2, 5, 7
+    x = torch.randn(B, H, W, cin, generator=g)
+    w = torch.randn(cin, cout, k, k, generator=g) / cin ** 0.5
+    dy = torch.randn(B, H * k, W * k, cout, generator=g)
+    xr = x.double().permute(0, 3, 1, 2).requires_grad_(True)
+    wr = w.double().requires_grad_(True)
+    y_ref = F.conv_transpose2d(xr, wr, stride=k)
+    y_ref.backward(dy.double().permute(0, 3, 1, 2))
+    xg = x.cuda().requires_grad_(True)
+    wg = w.cuda().requires_grad_(True)
+    y = conv_grad.conv_transpose2d(xg, wg, k)
+    assert tuple(y.shape) == (B, H * k, W * k, cout)
+    assert float((y.detach().cpu().double().permute(0, 3, 1, 2) - y_ref.detach()).abs().max()) <= 1e-5 * float(y_ref.detach().abs().max())
+    y.backward(dy.cuda())
+    assert tuple(xg.grad.shape) == tuple(x.shape)
+    for name, got, want in (("dx", xg.grad.cpu().double().permute(0, 3, 1, 2), xr.grad), ("dw", wg.grad.cpu().double(), wr.grad)):
+        err = float((got - want).abs().max())
+        assert err <= 2e-5 * float(want.abs().max()), (name, err, float(want.abs().max()))
+
+
+@pytest.mark.parametrize("cin,k", [(87, 2), (64, 4)])
+def test_conv_transpose2d_autograd_exact_on_integers(cin, k):
+    g = torch.Generator().manual_seed(cin * k)
+    B, H, W, cout = 2, 4, 6, 64
+    x = torch.randint(-3, 4, (B, H, W, cin), generator=g).float()
+    w = torch.randint(-3, 4, (cin, cout, k, k), generator=g).float()
+    dy = torch.randint(-3, 4, (B, H * k, W * k, cout), generator=g).float()
+    xr = x.double().permute(0, 3, 1, 2).requires_grad_(True)
+    wr = w.double().requires_grad_(True)
+    y_ref = F.conv_transpose2d(xr, wr, stride=k)
+    y_ref.backward(dy.double().permute(0, 3, 1, 2))
+    xg = x.cuda().requires_grad_(True)
+    wg = w.cuda().requires_grad_(True)
+    y = conv_grad.conv_transpose2d(xg, wg, k)
+    y.backward(dy.cuda())
+    assert torch.equal(y.detach().cpu().double().permute(0, 3, 1, 2), y_ref.detach())
+    assert torch.equal(xg.grad.cpu().double().permute(0, 3, 1, 2), xr.grad)
+    assert torch.equal(wg.grad.cpu().double(), wr.grad)
+
+
 def test_stem_weight_gradient_with_padded_image_channels():
     """The image stem: 3 weight channels over a 4-channel (zero-padded) NHWC image, taps packed into the tile columns."""
     g = torch.Generator().manual_seed(4)
