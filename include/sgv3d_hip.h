@@ -1000,6 +1000,19 @@ int sgv3d_deform_im2col3x3_backward(int batch, int h, int w, int channels, int g
                                     const float *offset, int off_ld, const float *grad_col, float *grad_x,
                                     float *grad_offset, int grad_off_ld, void *stream);
 
+/* The same adjoint, deterministic: grad_x in gather form, no float atomics -- a plan lists the in-range samples of every
+ * top-left corner of a (H + 1) x (W + 1) grid per image in ascending sample order, then one wave per input pixel sums its
+ * four lists in a fixed order.  grad_x and grad_offset are functions of the inputs only (bitwise repeatable); grad_offset
+ * is what sgv3d_deform_im2col3x3_backward writes.  Arguments as there, plus a scratch workspace of
+ * sgv3d_deform_im2col3x3_backward_det_workspace_bytes(batch, h, w) bytes (0: shape out of range) -- sized from the shape
+ * alone; no host synchronisation (capturable).  grad_col and grad_x 16-byte aligned.  Too small a workspace:
+ * SGV3D_ENOSPACE, nothing launched. */
+size_t sgv3d_deform_im2col3x3_backward_det_workspace_bytes(int batch, int h, int w);
+int sgv3d_deform_im2col3x3_backward_det(int batch, int h, int w, int channels, int groups, const float *x,
+                                        const float *offset, int off_ld, const float *grad_col, float *grad_x,
+                                        float *grad_offset, int grad_off_ld, void *workspace, size_t workspace_bytes,
+                                        void *stream);
+
 /* ================================================================================================
  * Image preprocessing (csrc/preprocess.hip): decoded uint8 camera frames -> model input
  * ================================================================================================ */

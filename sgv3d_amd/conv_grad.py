@@ -215,7 +215,7 @@ def _wgrad_choice(lib, d, x, dy, bf16=False):
     if sig in hip_ops.TUNE_DB and not (sig in hip_ops._COMMITTED_SIGS and not hip_ops._is_gfx950(x.device)):
         _WGRAD_DB[key] = tuple(hip_ops.TUNE_DB[sig])
         return _WGRAD_DB[key]
-    if torch.cuda.is_current_stream_capturing():
+    if torch.cuda.is_current_stream_capturing() or hip_ops.deterministic():
         return 0, 0
     pixels = d.batch * d.out_h * d.out_w
     cands = [(0, 0)]

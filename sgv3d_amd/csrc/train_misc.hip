@@ -10,6 +10,8 @@
 //   sgv3d_deform_im2col3x3_backward   adjoint of the deformable bilinear im2col of mmcv's DeformConv2dPack
 //        (lss_fpn.py:190-198): d loss / d offsets (one wave per (pixel, tap), channels reduced in fixed order) and
 //        d loss / d input (scatter to the four corners with float atomics, like mmcv's deformable_col2im).
+//   sgv3d_deform_im2col3x3_backward_det   the same adjoint with d loss / d input in gather form (a per-corner list of samples,
+//        then one wave per input pixel summing its lists in a fixed order): no float atomics, bitwise repeatable.
 //
 // All HBM-bound streaming work: one read of the operands, one write of the results.
 #include "common.hpp"
@@ -105,7 +107,8 @@ __global__ __launch_bounds__(kT) void dense_bwd_weight_kernel(int B, int K, int 
 
 // ------------------------------------------------------------------------------------------------ deformable im2col adjoint
 // one wave per (pixel, tap); lanes walk consecutive channels.  dcol uses the layout of sgv3d_deform_im2col3x3:
-// [pixel][group][tap][channels per group].
+// [pixel][group][tap][channels per group].  kAtomicDx = false: d offset only (the deterministic path gathers dx itself).
+template <bool kAtomicDx>
 __global__ __launch_bounds__(kT) void deform_im2col_bwd_kernel(int B, int H, int W, int C, int groups,
                                                               const float *__restrict__ x, const float *__restrict__ off,
                                                               int off_ld, const float *__restrict__ dcol,
@@ -148,10 +151,12 @@ __global__ __launch_bounds__(kT) void deform_im2col_bwd_kernel(int B, int H, int
             // d val / d hf = hw (v3 - v1) + lw (v4 - v2);  d val / d wf = hh (v2 - v1) + lh (v4 - v3)
             gy += d * (hw * (v3 - v1) + lw * (v4 - v2));
             gx += d * (hh * (v2 - v1) + lh * (v4 - v3));
-            if (ok1) __hip_atomic_fetch_add(dx + o1 + c, w1 * d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (ok2) __hip_atomic_fetch_add(dx + o2 + c, w2 * d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (ok3) __hip_atomic_fetch_add(dx + o3 + c, w3 * d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (ok4) __hip_atomic_fetch_add(dx + o4 + c, w4 * d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (kAtomicDx) {
+                if (ok1) __hip_atomic_fetch_add(dx + o1 + c, w1 * d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (ok2) __hip_atomic_fetch_add(dx + o2 + c, w2 * d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (ok3) __hip_atomic_fetch_add(dx + o3 + c, w3 * d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (ok4) __hip_atomic_fetch_add(dx + o4 + c, w4 * d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
         }
     }
     for (int o = 32; o > 0; o >>= 1) {                            // butterfly: the same order for every lane, every run
@@ -162,6 +167,176 @@ __global__ __launch_bounds__(kT) void deform_im2col_bwd_kernel(int B, int H, int
         doff[p * doff_ld + 2 * tap] = gy;
         doff[p * doff_ld + 2 * tap + 1] = gx;
     }
+}
+
+// ------------------------------------------------------------------------------------------------ deformable im2col adjoint, gather form
+// d loss / d x without float atomics.  Sample s = p * 9 + tap (pixel p = (b, h, w)) that lands in range at (hf, wf) adds
+// w_k * dcol[s] to the four corners of (floor hf, floor wf).  The plan keys every in-range sample by that top-left corner on a
+// (H + 1) x (W + 1) grid per image (row / column -1 included) and lists each key's samples in ascending sample order: count ->
+// scan -> fill -> rank (a sample's place in its list is the number of smaller sample indices in it, so the list does not depend
+// on the order in which the fill's integer atomics handed out slots).  Then one wave per input pixel (y, x) sums its four lists
+// in a fixed order -- key (y, x) with w1, (y, x - 1) with w2, (y - 1, x) with w3, (y - 1, x - 1) with w4 -- lanes walking the
+// channels: every element of dx adds the same terms in the same order on every run.  Any pile-up is handled; the rank pass is
+// quadratic in the length of a list and a long list is summed by one wave (slow, not wrong, when offsets collapse).
+__device__ __forceinline__ int dcn_sample_key(int H, int W, const float *__restrict__ off, int off_ld, long long s, float &hf,
+                                              float &wf) {
+    const int tap = (int)(s % 9);
+    const long long p = s / 9;
+    const int w_ = (int)(p % W);
+    const int h_ = (int)((p / W) % H);
+    const int ky = tap / 3, kx = tap - ky * 3;
+    hf = (float)(h_ - 1 + ky) + off[p * off_ld + 2 * tap];        // as deform_im2col_bwd_kernel forms the position
+    wf = (float)(w_ - 1 + kx) + off[p * off_ld + 2 * tap + 1];
+    if (!(hf > -1.f && wf > -1.f && hf < (float)H && wf < (float)W)) return -1;     // (NaN: out of range)
+    return ((int)floorf(hf) + 1) * (W + 1) + (int)floorf(wf) + 1;
+}
+
+__global__ __launch_bounds__(kT) void zero_i32_kernel(long long n, int *__restrict__ p) {
+    const long long i = (long long)blockIdx.x * kT + threadIdx.x;
+    if (i < n) p[i] = 0;
+}
+
+__global__ __launch_bounds__(kT) void dcn_plan_count_kernel(long long n, int H, int W, const float *__restrict__ off, int off_ld,
+                                                           int *__restrict__ key, int *__restrict__ count) {
+    const long long s = (long long)blockIdx.x * kT + threadIdx.x;
+    if (s >= n) return;
+    float hf, wf;
+    const int k = dcn_sample_key(H, W, off, off_ld, s, hf, wf);
+    const long long b = s / (9LL * H * W);
+    const int gk = k < 0 ? -1 : (int)(b * (H + 1) * (W + 1) + k);
+    key[s] = gk;
+    if (gk >= 0) atomicAdd(count + gk, 1);                      // integers: the totals do not depend on the order
+}
+
+constexpr int kScanT = 1024;
+
+// one workgroup: start[i] = count[0] + .. + count[i - 1], start[n] = total (each thread scans a contiguous run of counts)
+__global__ __launch_bounds__(kScanT) void dcn_plan_scan_kernel(int n, const int *__restrict__ count, int *__restrict__ start) {
+    __shared__ int part[kScanT];
+    const int per = (n + kScanT - 1) / kScanT;
+    const int lo = (int)min((long long)n, (long long)threadIdx.x * per), hi = min(n, lo + per);
+    int sum = 0;
+    for (int i = lo; i < hi; ++i) sum += count[i];
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    for (int o = 1; o < kScanT; o <<= 1) {
+        const int v = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    int run = part[threadIdx.x] - sum;
+    for (int i = lo; i < hi; ++i) {
+        start[i] = run;
+        run += count[i];
+    }
+    if (threadIdx.x == kScanT - 1) start[n] = part[kScanT - 1];
+}
+
+// count[] runs back down to zero: slot = what is left of the count - 1
+__global__ __launch_bounds__(kT) void dcn_plan_fill_kernel(long long n, const int *__restrict__ key, const int *__restrict__ start,
+                                                          int *__restrict__ count, int *__restrict__ unsorted) {
+    const long long s = (long long)blockIdx.x * kT + threadIdx.x;
+    if (s >= n) return;
+    const int gk = key[s];
+    if (gk < 0) return;
+    const int slot = atomicSub(count + gk, 1) - 1;
+    unsorted[start[gk] + slot] = (int)s;
+}
+
+__global__ __launch_bounds__(kT) void dcn_plan_rank_kernel(long long n, const int *__restrict__ key, const int *__restrict__ start,
+                                                          const int *__restrict__ unsorted, int *__restrict__ sorted) {
+    const long long s = (long long)blockIdx.x * kT + threadIdx.x;
+    if (s >= n) return;
+    const int gk = key[s];
+    if (gk < 0) return;
+    const int lo = start[gk], hi = start[gk + 1];
+    int rank = 0;
+    for (int j = lo; j < hi; ++j) rank += unsorted[j] < (int)s;
+    sorted[lo + rank] = (int)s;
+}
+
+// one wave per input pixel; lane l of chunk c owns the float4 of channels 4 (c4_begin + 64 c + l) .. + 3
+template <int NCH>
+__global__ __launch_bounds__(kT) void deform_dx_gather_kernel(int B, int H, int W, int C4, int groups, int c4_begin,
+                                                             const float *__restrict__ off, int off_ld, const int *__restrict__ start,
+                                                             const int *__restrict__ sorted, const float4 *__restrict__ dcol,
+                                                             float4 *__restrict__ dx) {
+    const int lane = threadIdx.x & 63;
+    const long long pix = (long long)blockIdx.x * (kT / 64) + (threadIdx.x >> 6);
+    if (pix >= (long long)B * H * W) return;                     // wave-uniform
+    const int x_ = (int)(pix % W);
+    const long long t = pix / W;
+    const int y_ = (int)(t % H);
+    const int b = (int)(t / H);
+    const int cpg4 = C4 / groups;
+    bool ok[NCH];
+    long long col[NCH];                                          // place of the lane's float4 inside a sample's dcol row
+    float4 acc[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const int c4 = c4_begin + c * 64 + lane;
+        ok[c] = c4 < C4;
+        const int g = c4 / cpg4;
+        col[c] = (long long)g * 9 * cpg4 + (c4 - g * cpg4);
+        acc[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const long long G = (long long)(H + 1) * (W + 1);
+    for (int r = 0; r < 4; ++r) {
+        const long long gk = b * G + (long long)(y_ + 1 - (r >> 1)) * (W + 1) + (x_ + 1 - (r & 1));
+        const int lo = start[gk], hi = start[gk + 1];
+        for (int j0 = lo; j0 < hi; j0 += 64) {
+            // 64 samples of the list at a time: lane k finds sample j0 + k and its weight for this corner ...
+            int my_s = 0;
+            float my_w = 0.f;
+            if (j0 + lane < hi) {
+                my_s = sorted[j0 + lane];
+                float hf, wf;
+                dcn_sample_key(H, W, off, off_ld, my_s, hf, wf);
+                const float lh = hf - floorf(hf), lw = wf - floorf(wf);
+                const float hh = 1.f - lh, hw = 1.f - lw;
+                my_w = r == 0 ? hh * hw : r == 1 ? hh * lw : r == 2 ? lh * hw : lh * lw;
+            }
+            // ... and the wave adds them in list order
+            const int cnt = min(64, hi - j0);
+            for (int k = 0; k < cnt; ++k) {
+                const int s = __shfl(my_s, k, 64);
+                const float w = __shfl(my_w, k, 64);
+                const int p = s / 9, tap = s - p * 9;
+                const long long row = (long long)p * 9 * C4 + (long long)tap * cpg4;
+#pragma unroll
+                for (int c = 0; c < NCH; ++c) {
+                    if (!ok[c]) continue;
+                    const float4 d = dcol[row + col[c]];
+                    acc[c].x += w * d.x;
+                    acc[c].y += w * d.y;
+                    acc[c].z += w * d.z;
+                    acc[c].w += w * d.w;
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+        if (ok[c]) dx[pix * C4 + c4_begin + c * 64 + lane] = acc[c];
+}
+
+struct DcnPlanLayout {
+    long long nseg, n, count, start, key, unsorted, sorted, bytes;      // int32 element offsets, total bytes
+};
+
+DcnPlanLayout dcn_plan_layout(int batch, int h, int w) {
+    DcnPlanLayout L{};
+    auto up = [](long long v) { return (v + 63) / 64 * 64; };           // 256-byte pieces
+    L.nseg = (long long)batch * (h + 1) * (w + 1);
+    L.n = (long long)batch * h * w * 9;
+    L.count = 0;
+    L.start = L.count + up(L.nseg);
+    L.key = L.start + up(L.nseg + 1);
+    L.unsorted = L.key + up(L.n);
+    L.sorted = L.unsorted + up(L.n);
+    L.bytes = (L.sorted + up(L.n)) * 4;
+    return L;
 }
 
 __global__ __launch_bounds__(kT) void zero_f32_kernel(long long n4, float4 *__restrict__ p) {
@@ -295,7 +470,56 @@ extern "C" int sgv3d_deform_im2col3x3_backward(int batch, int h, int w, int chan
     const long long n4 = (long long)batch * h * w * channels / 4;
     hipLaunchKernelGGL(zero_f32_kernel, dim3(cdiv(n4, kT)), dim3(kT), 0, as_stream(stream), n4, reinterpret_cast<float4 *>(grad_x));
     const long long items = (long long)batch * h * w * 9;
-    hipLaunchKernelGGL(deform_im2col_bwd_kernel, dim3(cdiv(items, kT / 64)), dim3(kT), 0, as_stream(stream), batch, h, w, channels,
-                       groups, x, offset, off_ld, grad_col, grad_x, grad_offset, grad_off_ld);
+    hipLaunchKernelGGL(deform_im2col_bwd_kernel<true>, dim3(cdiv(items, kT / 64)), dim3(kT), 0, as_stream(stream), batch, h, w,
+                       channels, groups, x, offset, off_ld, grad_col, grad_x, grad_offset, grad_off_ld);
     return check_launch("deform_im2col_bwd_kernel");
+}
+
+extern "C" size_t sgv3d_deform_im2col3x3_backward_det_workspace_bytes(int batch, int h, int w) {
+    if (batch <= 0 || h <= 0 || w <= 0) return 0;
+    const DcnPlanLayout L = dcn_plan_layout(batch, h, w);
+    if (L.n >= 0x7fffffffLL || L.nseg >= 0x7fffffffLL) return 0;
+    return (size_t)L.bytes;
+}
+
+extern "C" int sgv3d_deform_im2col3x3_backward_det(int batch, int h, int w, int channels, int groups, const float *x,
+                                                   const float *offset, int off_ld, const float *grad_col, float *grad_x,
+                                                   float *grad_offset, int grad_off_ld, void *workspace, size_t workspace_bytes,
+                                                   void *stream) {
+    SGV3D_REQUIRE(batch > 0 && h > 0 && w > 0 && channels > 0 && groups > 0 && channels % (4 * groups) == 0 && off_ld >= 18 &&
+                      grad_off_ld >= 18,
+                  "deform_im2col3x3_backward_det: bad shape");
+    SGV3D_REQUIRE(x && offset && grad_col && grad_x && grad_offset && workspace, "deform_im2col3x3_backward_det: null pointer");
+    SGV3D_REQUIRE(((uintptr_t)grad_col | (uintptr_t)grad_x) % 16 == 0, "deform_im2col3x3_backward_det: grad_col / grad_x not 16-byte aligned");
+    const DcnPlanLayout L = dcn_plan_layout(batch, h, w);
+    SGV3D_REQUIRE(L.n < 0x7fffffffLL && L.nseg < 0x7fffffffLL, "deform_im2col3x3_backward_det: too many samples");
+    if (workspace_bytes < (size_t)L.bytes)
+        return fail(SGV3D_ENOSPACE, "deform_im2col3x3_backward_det: workspace of %zu bytes, %lld needed", workspace_bytes, L.bytes);
+    int *ws = static_cast<int *>(workspace);
+    int *count = ws + L.count, *start = ws + L.start, *key = ws + L.key, *unsorted = ws + L.unsorted, *sorted = ws + L.sorted;
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(zero_i32_kernel, dim3(cdiv(L.nseg, kT)), dim3(kT), 0, st, L.nseg, count);
+    hipLaunchKernelGGL(dcn_plan_count_kernel, dim3(cdiv(L.n, kT)), dim3(kT), 0, st, L.n, h, w, offset, off_ld, key, count);
+    hipLaunchKernelGGL(dcn_plan_scan_kernel, dim3(1), dim3(kScanT), 0, st, (int)L.nseg, count, start);
+    hipLaunchKernelGGL(dcn_plan_fill_kernel, dim3(cdiv(L.n, kT)), dim3(kT), 0, st, L.n, key, start, count, unsorted);
+    hipLaunchKernelGGL(dcn_plan_rank_kernel, dim3(cdiv(L.n, kT)), dim3(kT), 0, st, L.n, key, start, unsorted, sorted);
+    const int c4 = channels / 4, chunks = cdiv(c4, 64);
+    const long long pixels = (long long)batch * h * w;
+    const dim3 grid(cdiv(pixels, kT / 64));
+    const float4 *dcol4 = reinterpret_cast<const float4 *>(grad_col);
+    float4 *dx4 = reinterpret_cast<float4 *>(grad_x);
+    if (chunks == 1)
+        hipLaunchKernelGGL(deform_dx_gather_kernel<1>, grid, dim3(kT), 0, st, batch, h, w, c4, groups, 0, offset, off_ld, start, sorted,
+                           dcol4, dx4);
+    else if (chunks == 2)
+        hipLaunchKernelGGL(deform_dx_gather_kernel<2>, grid, dim3(kT), 0, st, batch, h, w, c4, groups, 0, offset, off_ld, start, sorted,
+                           dcol4, dx4);
+    else
+        for (int c0 = 0; c0 < c4; c0 += 4 * 64)
+            hipLaunchKernelGGL(deform_dx_gather_kernel<4>, grid, dim3(kT), 0, st, batch, h, w, c4, groups, c0, offset, off_ld, start,
+                               sorted, dcol4, dx4);
+    // d offset: the kernel of the default path without its scatter (fixed-order channel sums, as there)
+    hipLaunchKernelGGL(deform_im2col_bwd_kernel<false>, dim3(cdiv(L.n, kT / 64)), dim3(kT), 0, st, batch, h, w, channels, groups, x,
+                       offset, off_ld, grad_col, grad_x, grad_offset, grad_off_ld);
+    return check_launch("deform_im2col3x3_backward_det");
 }

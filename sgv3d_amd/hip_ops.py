@@ -24,6 +24,17 @@ PROFILE = None
 # bitwise reproducible results (measured choices can differ between runs with timing noise, which moves the
 # results by fp32 rounding since the algorithms sum in different orders); ~10 % slower.
 AUTOTUNE = not __import__("os").environ.get("SGV3D_NO_AUTOTUNE")
+# True (SGV3D_DETERMINISTIC=1), or torch.use_deterministic_algorithms(True) -- what Lightning's Trainer(deterministic=True)
+# sets --: training runs bitwise repeatable.  Read at every launch (a capture bakes in the value it saw): see deterministic().
+DETERMINISTIC = __import__("os").environ.get("SGV3D_DETERMINISTIC", "0") not in ("", "0")
+
+
+def deterministic():
+    """True in deterministic mode: the DCN input gradient is the gather-form kernel (no float atomics,
+    ``sgv3d_deform_im2col3x3_backward_det``) and no per-layer choice is made by timing -- a layer signature that is in
+    TUNE_DB takes its recorded choice, one that is not takes the fixed rule that SGV3D_NO_AUTOTUNE and a graph capture use.
+    Scope: bitwise repeatable on the same GPU model, software stack, world size and bucket size."""
+    return DETERMINISTIC or torch.are_deterministic_algorithms_enabled()
 # True: conv records carry the layer shape in their name (tools/layer_report.py)
 PROFILE_DETAIL = False
 # False: the autotuner never proposes split-K (experiments; SGV3D_NO_SPLITK=1)
@@ -644,7 +655,7 @@ class PackedConv:
                 if choice is not None:
                     self._tile_cache[key] = choice
                     TUNE_STATS["from_db"] += 1
-                elif AUTOTUNE and not torch.cuda.is_current_stream_capturing():
+                elif AUTOTUNE and not torch.cuda.is_current_stream_capturing() and not deterministic():
                     TUNE_STATS["measured"] += 1
                     choice = self._autotune(lib, d, x, residual, gate, out, gemm_m, gemm_n, nkt, t, sk, io)
                     self._tile_cache[key] = choice
@@ -1161,7 +1172,7 @@ def conv_pair_choice(a, b, x, residual=None):
         return True
     if sig in TUNE_DB and not (sig in _COMMITTED_SIGS and not _is_gfx950(x.device)):
         return bool(TUNE_DB[sig][0])
-    if torch.cuda.is_current_stream_capturing():
+    if torch.cuda.is_current_stream_capturing() or deterministic():
         return True
     act = torch.bfloat16
     two = lambda: b(a(x, out_dtype=act), residual=residual, out_dtype=act)

@@ -239,7 +239,7 @@ class BEVHeightHead(HipModule):
         hit = hip_ops.TUNE_DB.get(sig) if hip_ops.AUTOTUNE else None
         if hit is not None and ok.get(int(hit[0]) - 100, False):
             return int(hit[0]) - 100
-        if not hip_ops.AUTOTUNE or torch.cuda.is_current_stream_capturing():
+        if not hip_ops.AUTOTUNE or torch.cuda.is_current_stream_capturing() or hip_ops.deterministic():
             return 2 if f4_ok else 0
         cands = {0: lambda: hip_ops.centerhead_branches(shared, s['first'], s['w2'], s['b2'], s['out_begin'], s['nb']),
                  1: lambda: self._two_kernel_branches(s, shared), 2: lambda: self._fused_f4(s, shared)}

@@ -94,10 +94,23 @@ class _DeformIm2col(torch.autograd.Function):
         dcol = dcol.contiguous()
         dx = torch.empty_like(x)
         doff = torch.zeros_like(offset)
+        lib = _lib.load()
+        if hip_ops.deterministic():
+            # gather form of d x (no float atomics): bitwise repeatable
+            nws = lib.sgv3d_deform_im2col3x3_backward_det_workspace_bytes(B, H, W)
+            if nws == 0:
+                raise _lib.SGV3DError(f"deform_im2col3x3_backward_det: shape {B}x{H}x{W} out of range")
+            ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
+            with torch.cuda.device(x.device), prof("deform_im2col3x3_backward_det"):
+                rc = lib.sgv3d_deform_im2col3x3_backward_det(B, H, W, C, int(ctx.groups), x.data_ptr(), offset.data_ptr(),
+                                                             int(offset.shape[-1]), dcol.data_ptr(), dx.data_ptr(), doff.data_ptr(),
+                                                             int(doff.shape[-1]), ws.data_ptr(), nws, _st(x))
+            _lib.check(rc, "sgv3d_deform_im2col3x3_backward_det")
+            return dx, doff, None
         with torch.cuda.device(x.device), prof("deform_im2col3x3_backward"):
-            rc = _lib.load().sgv3d_deform_im2col3x3_backward(B, H, W, C, int(ctx.groups), x.data_ptr(), offset.data_ptr(),
-                                                             int(offset.shape[-1]), dcol.data_ptr(), dx.data_ptr(),
-                                                             doff.data_ptr(), int(doff.shape[-1]), _st(x))
+            rc = lib.sgv3d_deform_im2col3x3_backward(B, H, W, C, int(ctx.groups), x.data_ptr(), offset.data_ptr(),
+                                                     int(offset.shape[-1]), dcol.data_ptr(), dx.data_ptr(),
+                                                     doff.data_ptr(), int(doff.shape[-1]), _st(x))
         _lib.check(rc, "sgv3d_deform_im2col3x3_backward")
         return dx, doff, None
 

@@ -60,16 +60,30 @@ def multistep_lr(base_lr, epoch, milestones=(19, 23), gamma=0.1):
     return base_lr * gamma ** sum(1 for m in milestones if epoch >= m)
 
 
+_ADAMW_GROUP = None
+
+
+def _torch_adamw_group():
+    """The param-group keys and defaults torch.optim.AdamW of the installed torch writes (they differ between versions)."""
+    global _ADAMW_GROUP
+    if _ADAMW_GROUP is None:
+        g = torch.optim.AdamW([torch.zeros(1, requires_grad=True)]).state_dict()['param_groups'][0]
+        _ADAMW_GROUP = {k: v for k, v in g.items() if k != 'params'}
+    return dict(_ADAMW_GROUP)
+
+
 class FlatParams:
     def __init__(self, params, bucket_bytes=None):
         bucket_bytes = DEFAULT_BUCKET_BYTES if bucket_bytes is None else int(bucket_bytes)
-        params = [p for p in params if p.requires_grad]     # (frozen_stages: the image backbone's stem is not in any bucket)
+        self.all_params = list(params)                 # the caller's numbering, frozen ones included (torch.optim state_dict indices)
+        params = [p for p in self.all_params if p.requires_grad]     # (frozen_stages: the image backbone's stem is not in any bucket)
         assert params, "no trainable parameters"
         assert all(p.dtype == torch.float32 for p in params), "fp32 parameters only"
         self.params = params
         dev = params[0].device
         order = list(reversed(params))                 # backward reaches the last layers first
         self.buckets = []                              # (flat_param, flat_grad, [(param, offset, numel)])
+        self.where = {}                                # id(param) -> (bucket, offset, numel)
         cur, cur_n = [], 0
         limit = max(1, bucket_bytes // 4)
         for p in order:
@@ -89,6 +103,7 @@ class FlatParams:
             p.data = flat_p[off:off + cnt].view(p.shape)
             p.grad = flat_g[off:off + cnt].view(p.shape)
             grad_slots.register(p.data_ptr(), flat_g, off, cnt, p.shape)
+            self.where[id(p)] = (len(self.buckets), off, cnt)
         self.buckets.append((flat_p, flat_g, entries))
 
     def zero_grad(self):
@@ -121,7 +136,7 @@ class DataParallelAdamW:
     def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-7, bucket_bytes=None, group=None,
                  max_grad_norm=None):
         self.flat = params if isinstance(params, FlatParams) else FlatParams(params, bucket_bytes)
-        self.lr, self.betas, self.eps, self.weight_decay = float(lr), betas, float(eps), float(weight_decay)
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), tuple(betas), float(eps), float(weight_decay)
         self.group = group
         self.max_grad_norm = None if not max_grad_norm else float(max_grad_norm)     # None / 0: no clipping (Lightning's default)
         self._clip = None             # device [coefficient, total norm] of the step that ran last
@@ -139,8 +154,81 @@ class DataParallelAdamW:
     def broadcast_parameters(self, src=0):
         """Every rank takes rank ``src``'s parameters (one broadcast per flat bucket)."""
         import torch.distributed as dist
+        if self.packs is not None:
+            self.packs.close()          # the buckets are written behind torch's version counters: kept packed forms are stale
         for p, _, _ in self.flat.buckets:
             dist.broadcast(p, src=src, group=self.group)
+
+    # ------------------------------------------------------------------ optimiser state in torch.optim.AdamW's layout
+    def _name(self, i):
+        names = getattr(self, 'param_names', None)
+        p = self.flat.all_params[i]
+        return f"parameter {i}" + (f" ({names[i]})" if names and i < len(names) else "") + f" of shape {list(p.shape)}"
+
+    def state_dict(self):
+        """``torch.optim.AdamW(params).state_dict()`` of this optimiser: ``state[i] = {'step', 'exp_avg', 'exp_avg_sq'}`` with
+        ``i`` the position in the iterable given to the constructor (frozen parameters included, and without state), one param
+        group with torch's keys.  A parameter whose two moments are all zero -- it never had a non-zero gradient -- carries no
+        state, as in torch.  Per parameter: independent of bucket size and world size.  Tensors are copies."""
+        state = {}
+        if self.steps > 0:
+            live = {}
+            for bi, ((_, _, entries), (m, v)) in enumerate(zip(self.flat.buckets, self.state)):
+                flags = torch.stack([(m[off:off + cnt] != 0).any() | (v[off:off + cnt] != 0).any() for _, off, cnt in entries])
+                live.update(zip((id(p) for p, _, _ in entries), flags.tolist()))
+            for i, p in enumerate(self.flat.all_params):
+                loc = self.flat.where.get(id(p))
+                if loc is None or not live[id(p)]:
+                    continue
+                bi, off, cnt = loc
+                m, v = self.state[bi]
+                state[i] = {'step': torch.tensor(float(self.steps)), 'exp_avg': m[off:off + cnt].view(p.shape).clone(),
+                            'exp_avg_sq': v[off:off + cnt].view(p.shape).clone()}
+        group = dict(_torch_adamw_group(), lr=self.lr, betas=tuple(self.betas), eps=self.eps, weight_decay=self.weight_decay,
+                     params=list(range(len(self.flat.all_params))))
+        return {'state': state, 'param_groups': [group]}
+
+    def load_state_dict(self, state_dict):
+        """Load ``state_dict()`` of this class or of ``torch.optim.AdamW`` over the same parameter list (``step`` as an int,
+        torch 1.9, or a tensor, torch 2.x).  Parameters without an entry get zero moments.  A different parameter count, a
+        moment of another shape, state on a frozen parameter or entries with different steps raise before anything is
+        written.  Hyperparameters (lr, betas, eps, weight_decay) are taken from the state, as torch does."""
+        groups = state_dict['param_groups']
+        if len(groups) != 1:
+            raise _lib.SGV3DError(f"optimizer state has {len(groups)} param groups; this optimiser has one")
+        group, n = groups[0], len(self.flat.all_params)
+        if len(group['params']) != n:
+            raise _lib.SGV3DError(f"optimizer state is for {len(group['params'])} parameters; this optimiser has {n}")
+        index = {pid: i for i, pid in enumerate(group['params'])}
+        steps, writes = set(), []
+        for key, entry in state_dict['state'].items():
+            if key not in index:
+                raise _lib.SGV3DError(f"optimizer state has an entry for unknown parameter id {key}")
+            i = index[key]
+            p = self.flat.all_params[i]
+            loc = self.flat.where.get(id(p))
+            if loc is None:
+                raise _lib.SGV3DError(f"optimizer state for {self._name(i)}, which does not train here")
+            for k in ('exp_avg', 'exp_avg_sq'):
+                if tuple(entry[k].shape) != tuple(p.shape):
+                    raise _lib.SGV3DError(f"optimizer state for {self._name(i)}: {k} has shape {list(entry[k].shape)}")
+            s = entry['step']
+            steps.add(int(s) if isinstance(s, int) else int(round(float(s))))
+            writes.append((loc, entry))
+        if len(steps) > 1:
+            raise _lib.SGV3DError(f"optimizer state entries have different step counts {sorted(steps)}; the fused update keeps one")
+        if self.packs is not None:
+            self.packs.close()
+        for m, v in self.state:
+            m.zero_()
+            v.zero_()
+        for (bi, off, cnt), entry in writes:
+            m, v = self.state[bi]
+            m[off:off + cnt].copy_(entry['exp_avg'].reshape(-1))
+            v[off:off + cnt].copy_(entry['exp_avg_sq'].reshape(-1))
+        self.steps = steps.pop() if steps else 0
+        self.lr, self.betas = float(group['lr']), tuple(float(b) for b in group['betas'])
+        self.eps, self.weight_decay = float(group['eps']), float(group['weight_decay'])
 
     def check_replicas(self):
         """Raise if the parameters differ between ranks (sum and sum of squares of every bucket, compared through one
@@ -375,9 +463,15 @@ class GraphedTrainStep:
 
     Construction runs ``warmup`` REAL eager steps on the capture stream first (allocator pools, lazily created state), then records;
     the recorded step itself first runs at the first call.  ``graphed()`` returns the (static) loss tensor; ``graphed.result`` is the
-    same tensor."""
+    same tensor.
 
-    def __init__(self, forward_backward, opt, lr=None, warmup=1, strict=False):
+    ``keep_state`` (opt-in; a module, normally the model): the warm-up steps leave the training state as they found it -- the
+    parameters, AdamW moments and step counter, the module's buffers (BatchNorm statistics) and torch's CPU and GPU random
+    state are restored before the capture -- so the first replay is the step a run resumed from a checkpoint takes next.
+    (The capture itself does not advance the GPU generator; every replay advances it by the recorded step's offsets, as
+    the eager step does.)"""
+
+    def __init__(self, forward_backward, opt, lr=None, warmup=1, strict=False, keep_state=None):
         self.fn, self.opt = forward_backward, opt
         self.result = None
         self.graph = None
@@ -396,11 +490,28 @@ class GraphedTrainStep:
             for h in opt._hooks:
                 h.remove()
             opt._hooks = []
+        snap = None
+        if keep_state is not None and int(warmup) > 0:
+            snap = ([p.clone() for p, _, _ in opt.flat.buckets], [(m.clone(), v.clone()) for m, v in opt.state], opt.steps,
+                    [(b, b.clone()) for b in keep_state.buffers()], torch.get_rng_state(), torch.cuda.get_rng_state(dev))
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             for _ in range(max(0, int(warmup))):      # on the capture stream: allocator pools, lazily created state
                 self._eager(lr)
+            if snap is not None:
+                if opt.packs is not None:
+                    opt.packs.close()
+                for (p, _, _), q in zip(opt.flat.buckets, snap[0]):
+                    p.copy_(q)
+                for (m, v), (m0, v0) in zip(opt.state, snap[1]):
+                    m.copy_(m0)
+                    v.copy_(v0)
+                opt.steps = snap[2]
+                for b, b0 in snap[3]:
+                    b.copy_(b0)
+                torch.set_rng_state(snap[4])
+                torch.cuda.set_rng_state(snap[5], dev)
             side.synchronize()
             g = torch.cuda.CUDAGraph()
             steps_before = opt.steps

@@ -32,6 +32,8 @@ ap.add_argument("--clip", type=float, default=5.0, help="global gradient-norm bo
                 "exps/bevheight/dair-v2x/bev_height_lss_r50_864_1536_256x256.py:405); 0 = off")
 ap.add_argument("--bucket-mib", type=int, default=None, help="flat gradient bucket size (default train_step.DEFAULT_BUCKET_BYTES = 48 MiB)")
 ap.add_argument("--profile", action="store_true", help="per-kernel-family times of one step (HIP events, eager)")
+ap.add_argument("--checkpoint", default=None, help="after the timed steps: time save_checkpoint to this file and load_checkpoint "
+                "back into the model and optimiser (sgv3d_amd/checkpoint.py)")
 args = ap.parse_args()
 
 if args.dtype == "bf16":
@@ -178,6 +180,17 @@ if args.profile:
     out["profiled_step_ms"] = 1e3 * wall
     out["hip_kernels_ms"] = {k: {"ms": round(v[0], 2), "launches": v[2], "tflops": round(v[1] / v[0] / 1e9, 1) if v[0] > 0 and v[1] > 0 else None}
                              for k, v in sorted(fam.items(), key=lambda kv: -kv[1][0])}
+if args.checkpoint:
+    from sgv3d_amd.checkpoint import load_checkpoint, save_checkpoint
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    save_checkpoint(args.checkpoint, model, opt, epoch=0, global_step=opt.steps)
+    t1 = time.perf_counter()
+    load_checkpoint(args.checkpoint, model, opt)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    out.update(checkpoint_save_s=t1 - t0, checkpoint_load_s=t2 - t1, checkpoint_mb=os.path.getsize(args.checkpoint) / 2**20,
+               deterministic=hip_ops.deterministic())
 hip_ops.save_tune_db()          # no-op unless SGV3D_TUNE_CACHE is set (tools/profile_train.sh)
 group.close()
 if group.rank == 0:
