@@ -117,8 +117,9 @@ class _Bits:
         return v
 
 
-def coefficients(info):
-    """libjpeg's sequential decode -> int64 [blocks, 64] natural order, DC predicted."""
+def coefficients(info, trace=None):
+    """libjpeg's sequential decode -> int64 [blocks, 64] natural order, DC predicted.  ``trace``: a list that receives
+    (class, code length, symbol) of every Huffman code in decode order."""
     scan = info['scan']
     ri = info['restart']
     # the intervals: split at RSTn markers
@@ -146,12 +147,12 @@ def coefficients(info):
             rd, pred = _Bits(segs[si]), [0, 0, 0]
         for b, (comp, dct, act) in enumerate(bt):
             blk = coef[m * info['bpm'] + b]
-            s = _huff(rd, dct)
+            s = _huff(rd, dct, trace, 0)
             pred[comp] += _extend(rd.get(s), s)
             blk[0] = pred[comp]
             k = 1
             while k < 64:
-                rs = _huff(rd, act)
+                rs = _huff(rd, act, trace, 1)
                 r, s = rs >> 4, rs & 15
                 if s:
                     k += r
@@ -164,11 +165,13 @@ def coefficients(info):
     return coef
 
 
-def _huff(rd, table):
+def _huff(rd, table, trace=None, cls=0):
     code = 0
     for ln in range(1, 17):
         code = (code << 1) | rd.get(1)
         if (ln, code) in table:
+            if trace is not None:
+                trace.append((cls, ln, table[(ln, code)]))
             return table[(ln, code)]
     raise ValueError("bad Huffman code")
 
@@ -184,6 +187,7 @@ class _Machine:
         self.bpm = info['bpm']
         bt = _block_tables(info)
         self.tab = [(d, a) for _, d, a in bt]
+        self.err = 0   # the kernel's status bits met so far: 1 bad code, 2 coefficient past 63, 4 short, 8 marker
 
     def _byte(self, i):
         return self.s[i] if i < self.n else None
@@ -199,6 +203,7 @@ class _Machine:
         """-> (new state, DC code?, coefficient (zigzag index, value) or None)"""
         pos, b, k = st
         byte0, sh = pos >> 3, pos & 7
+        self.rst = False   # (True after a step that took a restart marker)
         # destuffed bytes from byte0 (raw offset of each), up to the first marker / the end
         dbytes, raws, r = [], [], 0
         while len(dbytes) < 5:
@@ -220,7 +225,11 @@ class _Machine:
         q = 1 if sh else 0
         ones = (1 << (8 - sh)) - 1
         if mk == q and (sh == 0 or (dbytes[0] & ones) == ones):
-            return (self._marker(byte0 + (raws[1] if q and len(raws) > 1 else (mraw if q else 0))), 0, 0), False, None
+            if b or k:
+                self.err |= 8
+            after = self._marker(byte0 + (raws[1] if q and len(raws) > 1 else (mraw if q else 0)))
+            self.rst = after < self.bits
+            return (after, 0, 0), False, None
         acc = 0
         for i in range(5):
             acc = (acc << 8) | (dbytes[i] if i < mk else 0)
@@ -233,9 +242,11 @@ class _Machine:
                 break
         if ln is None:
             ln, sym = 16, 0
+            self.err |= 1
         ns = sym & 15
         nb = ln + ns
         if sh + nb > 8 * mk:
+            self.err |= 4
             return (self._marker(byte0 + mraw), 0, 0), False, None
         val = _extend(((peek << ln) & 0xFFFFFFFF) >> (32 - ns), ns) if ns else 0
         o2 = sh + nb
@@ -249,10 +260,13 @@ class _Machine:
             run = sym >> 4
             if ns == 0:
                 k = k + 16 if run == 15 else 64
+                if k > 64:
+                    self.err |= 2
                 k = min(k, 64)
             else:
                 k += run
                 if k > 63:
+                    self.err |= 2
                     k = 64
                 else:
                     co, k = (k, val), k + 1

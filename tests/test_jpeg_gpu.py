@@ -1,7 +1,10 @@
 """GPU: the JPEG decode (csrc/jpeg.hip) byte for byte against Pillow's decode (tests/golden/jpeg.npz: small files whole,
 1080x1920 files by row CRC32) at several subsequence lengths, mixed batches, repeatability, the decode fed into
 ImagePreprocessor, graph capture with restaging, FramePipeline(decode=), a corrupt frame contained by its status word,
-and argument errors raised before any launch."""
+and argument errors raised before any launch.  The stress fixture (tests/golden/jpeg_stress.npz: edge sizes, noise,
+constant and high-frequency content, re-coded Huffman tables, fill bytes, odd restart intervals, frames that cross the
+kernels' chunk sizes): every file byte-exact at several subsequence lengths, mixed batches, reused buffers, and
+structured corruptions contained by the status word."""
 import os
 import zlib
 
@@ -10,6 +13,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+import jpeg_recode as C
 import preprocess_ref as P
 from sgv3d_amd import synthetic as S
 
@@ -178,3 +182,135 @@ def test_errors_before_any_launch(fixture):
         dec([_jpg(fixture, 's420_61x83')], seq_bytes=4)
     with pytest.raises(RuntimeError, match='nothing decoded'):
         dec.status()
+
+
+# ---------------------------------------------------------------------------------------------- the stress fixture
+STRESS = np.load(os.path.join(GOLDEN, "jpeg_stress.npz"))
+STRESS_NAMES = C.case_names(STRESS)
+STRESS_SMALL = [n for n in STRESS_NAMES if not n.startswith('big_')]
+STRESS_ENTROPY = [n for n in STRESS_NAMES if n.startswith(('cc', 'cx', 'rc_'))]   # content classes and re-coded files
+MIXED_420 = ('cc420_noise_q100_r1', 'rc_noise_long', 'cc420_const_r3', 'rc_noise_split', 'rc_const_long',
+             'cc420_zrl_r6', 'rc_noise_src', 'cc420_bw8_r0', 'rc_const_split', 'rc_noise_fill3', 'rc_noise_combo',
+             'cc420_noise_q100_r0')
+CORRUPT_SOURCES = ('cc420_noise_q100_r1', 'rc_scene420_fill1')
+
+
+def _sjpg(name):
+    return STRESS[f'{name}_jpg'].tobytes()
+
+
+def _hw(name):
+    kind, want = C.expected(STRESS, name)
+    if kind == 'rgb':
+        return want.shape[:2]
+    from sgv3d_amd.jpeg import parse
+    rec, _ = parse(_sjpg(name))
+    return int(rec['height']), int(rec['width'])
+
+
+def _assert_frame(got, name, what=''):
+    """got: uint8 [h, w, 3] numpy == Pillow's decode of the case (whole, or by row CRC32)"""
+    kind, want = C.expected(STRESS, name)
+    if kind == 'crc':
+        bad = np.nonzero(_row_crc(got) != want)[0]
+        assert got.shape[0] == want.shape[0] and bad.size == 0, (f"{name} {what}: {bad.size} rows differ, first "
+                                                                 f"{bad[:10].tolist()}")
+        return
+    assert got.shape == want.shape, (name, got.shape, want.shape)
+    diff = np.argwhere(got != want)
+    assert diff.shape[0] == 0, (f"{name} {what}: {diff.shape[0]} bytes differ, first at (row, column, channel) "
+                                f"{tuple(diff[0].tolist())}: {got[tuple(diff[0])]} != {want[tuple(diff[0])]}")
+
+
+@pytest.mark.parametrize("name", STRESS_SMALL)
+def test_stress_small_files_byte_exact(name):
+    dec = _dec(_hw(name), max_bytes=1 << 17)
+    got = dec([_sjpg(name)])
+    _assert_frame(got[0].cpu().numpy(), name)
+    assert dec.status().tolist() == [0]
+
+
+@pytest.mark.parametrize("name", STRESS_ENTROPY)
+def test_stress_subsequence_lengths_agree(name):
+    """8, 9 and 13 bytes, the default, a long one, and one subsequence for the whole scan."""
+    dec = _dec(_hw(name), max_bytes=1 << 17)
+    outs = []
+    for s in (8, 9, 13, 64, 1024, 1 << 17):
+        outs.append(dec([_sjpg(name)], seq_bytes=s)[0].cpu())
+        assert dec.status().tolist() == [0], (name, s)
+    for o in outs[1:]:
+        assert torch.equal(o, outs[0])
+    _assert_frame(outs[0].numpy(), name)
+
+
+@pytest.mark.parametrize("order", [tuple(range(12)), (11, 3, 7, 0, 9, 1, 5, 10, 2, 8, 4, 6)])
+def test_stress_mixed_batches(order):
+    """64x96 4:2:0 files with different restart intervals, table sets (same, long, split), fill bytes and content in
+    one batch: every frame equals its single-file decode and the fixture; a second run is bitwise equal."""
+    names = [MIXED_420[i] for i in order]
+    files = [_sjpg(n) for n in names]
+    dec = _dec((64, 96), max_bytes=1 << 15)
+    batch = dec(files, lead=(2, 3, 2)).cpu()
+    assert dec.status().tolist() == [0] * 12
+    flat = batch.view(12, 64, 96, 3)
+    for i, n in enumerate(names):
+        assert torch.equal(flat[i], dec([files[i]])[0].cpu()), n
+        _assert_frame(flat[i].numpy(), n, 'in a mixed batch')
+    assert torch.equal(dec(files, lead=(2, 3, 2)).cpu(), batch)
+
+
+@pytest.mark.parametrize("seq_bytes", [8, 64])
+def test_stress_chunk_crossers_by_row_crc(seq_bytes):
+    """1024x1040 4:2:0: 16640 luma blocks (more than one chunk of the DC scan), 65 MCUs per row at restart interval 7
+    (more than eight intervals, none ends a row), with the file's tables and with long codes."""
+    names = ('big_1024x1040_r7', 'big_1024x1040_r7_long')
+    dec = _dec((1024, 1040), max_bytes=1 << 17)
+    got = dec([_sjpg(n) for n in names], seq_bytes=seq_bytes).cpu().numpy()
+    for i, n in enumerate(names):
+        _assert_frame(got[i], n, f'seq_bytes={seq_bytes}')
+    assert dec.status().tolist() == [0, 0]
+
+
+def test_stress_large_frame_by_row_crc():
+    dec = _dec((2176, 3840))
+    got = dec([_sjpg('big_2176x3840')]).cpu().numpy()
+    _assert_frame(got[0], 'big_2176x3840')
+    assert dec.status().tolist() == [0]
+
+
+def test_stress_reused_buffers_do_not_leak():
+    """A long noise scan, then a constant-colour scan of a few hundred bytes, then noise again through one decoder
+    and one set of persistent buffers: stale exits / sync / base entries of the longer scan must not reach the
+    short one."""
+    from sgv3d_amd.jpeg import JpegStaging
+    names = ('cc420_noise_q100_r0', 'cc420_const_r0', 'cc420_noise_q100_r1', 'rc_const_long', 'rc_noise_edge9')
+    dec = _dec((64, 96), max_bytes=1 << 15, seq_bytes=8)
+    st = JpegStaging(dec, (1,))
+    for n in names:
+        _assert_frame(dec([_sjpg(n)])[0].cpu().numpy(), n, 'through a reused decoder')
+        assert dec.status().tolist() == [0]
+        st.stage([_sjpg(n)])
+        out = st.launch()
+        torch.cuda.synchronize()
+        _assert_frame(out[0].cpu().numpy(), n, 'through reused buffers')
+        assert st.status().tolist() == [0]
+
+
+@pytest.mark.parametrize("src", CORRUPT_SOURCES)
+def test_stress_corruptions_are_reported_and_contained(src):
+    """One flipped bit, a zeroed last quarter and an overwritten restart marker (each first run on the restatement's
+    machine by tests/test_jpeg_cpu.py): the batch completes, the good frames around the corrupt one are byte-exact and
+    the corrupt frame's status is non-zero wherever the model reports an error."""
+    good = _sjpg(src)
+    other = 'cc420_zrl_r1' if src.startswith('cc') else 'rc_scene420_split'
+    hw = _hw(src)
+    for what, bad in C.corruptions(good).items():
+        for seq in (8, 64):
+            model = C.model_status(bad, seq)
+            dec = _dec(hw, max_bytes=1 << 15)
+            out = dec([good, bad, _sjpg(other)], seq_bytes=seq).cpu().numpy()
+            st = dec.status()
+            assert st[0] == 0 and st[2] == 0, (what, seq, st)
+            assert model == 0 or st[1] != 0, (what, seq, st, model)
+            _assert_frame(out[0], src, f'next to {what}')
+            _assert_frame(out[2], other, f'next to {what}')
