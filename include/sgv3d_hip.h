@@ -475,6 +475,26 @@ int sgv3d_deform_conv3x3_forward(int batch, int h, int w, int channels, int grou
                                  const float *offset, int off_ld, const float *const *w_packed, int k_pad, int cout_pad,
                                  float *y, int y_ld, int y_coff, void *stream);
 
+/* The same layer in ONE launch on the bf16 matrix cores (csrc/dcn_fused_bf16.hip): the bf16-mode twin of
+ * sgv3d_deform_conv3x3_forward.  The bilinear sample is computed in f32 from the loaded values exactly as
+ * sgv3d_deform_im2col3x3_bf16 (bf16 x) / sgv3d_deform_im2col3x3 (f32 x) compute it and rounded once to bf16 (nearest even); the
+ * weights are rounded once to bf16 by the pack entry; products on v_mfma_f32_16x16x32_bf16, f32 accumulation in ascending
+ * (tap, channel) order, no split along k: two calls give identical bits.
+ *   x NHWC [B, H, W, C], bf16 (x_is_bf16 != 0) or f32; offset f32 [B, H, W, off_ld >= 18], (dy, dx) of tap t at 2t, 2t+1
+ *   w_packed: sgv3d_deform_conv3x3_bf16_weight_bytes(C, groups, out_per_group) bytes (0: shape not covered) written by
+ *             sgv3d_deform_conv3x3_bf16_pack_weight from the layer's f32 OIHW weights [groups * out_per_group][C/groups][3][3]
+ *   y [B, H, W, y_ld], f32 or bf16 (y_is_bf16 != 0: the f32 accumulator rounded once): channels
+ *     [y_coff, y_coff + groups * out_per_group) written and nothing else
+ * C/groups % 32 == 0, out_per_group % 4 == 0, groups <= 8, y_ld % 4 == 0, y_coff % 4 == 0, any B * H * W; x and w_packed below
+ * 2 GiB each; 16-byte aligned x, y, w_packed.  Enqueues on `stream` only, allocates nothing; bad arguments are refused before
+ * any HIP call. */
+size_t sgv3d_deform_conv3x3_bf16_weight_bytes(int channels, int groups, int out_per_group);
+int sgv3d_deform_conv3x3_bf16_pack_weight(const float *weight, int channels, int groups, int out_per_group, void *w_packed,
+                                          void *stream);
+int sgv3d_deform_conv3x3_forward_bf16(int batch, int h, int w, int channels, int groups, int out_per_group, const void *x,
+                                      int x_is_bf16, const float *offset, int off_ld, const void *w_packed, void *y,
+                                      int y_is_bf16, int y_ld, int y_coff, void *stream);
+
 /* Deformable 3x3 sampling of mmcv DeformConv2dPack (DCNv1, deform_groups=1, stride 1, pad 1, dil 1;
  * lss_fpn.py:190-198): col[b, p, g, tap, cg] = bilinear(x[b, :, :, g*cpg + cg], p + tap + offset).
  *   x      f32 [B, H, W, C] NHWC;  offset f32 [B, H, W, off_ld] with (dy, dx) of tap t at 2t, 2t+1

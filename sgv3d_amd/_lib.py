@@ -121,6 +121,10 @@ _PROTOS = {
     "sgv3d_deform_im2col3x3": (c_int, [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "sgv3d_deform_conv3x3_forward": (c_int, [c_int] * 6 + [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
                                                           c_void_p]),
+    "sgv3d_deform_conv3x3_bf16_weight_bytes": (c_size_t, [c_int] * 3),
+    "sgv3d_deform_conv3x3_bf16_pack_weight": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "sgv3d_deform_conv3x3_forward_bf16": (c_int, [c_int] * 6 + [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                                               c_void_p]),
     "sgv3d_head_final_conv": (c_int, [c_int] * 6 + [c_void_p] * 6),
     "sgv3d_centerpoint_decode_workspace_bytes": (c_size_t, [c_int] * 3),
     "sgv3d_centerpoint_decode": (c_int, [c_int] * 5 + [c_void_p] * 6 + [c_ll] + [ctypes.c_float] * 6 +

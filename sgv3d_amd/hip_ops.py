@@ -1125,7 +1125,8 @@ def switch_state():
     g = globals()
     return tuple(g.get(k) for k in ("AUTOTUNE", "SPLIT_K", "WINOGRAD", "FUSED_HEAD", "HEAD_PATH", "MFMA_BF16", "BF16_ACTIVATIONS",
                                     "MFMA_F32X3", "MFIRST", "WINO4", "WINO_HALF", "PATCH_BF16", "DW_BF16", "DW_DEEP", "DW_NARROW",
-                                    "DW_SPLIT_K", "DW_DEEP_MAX_WGS", "PAIR_BF16", "TUNE_STREAMS", "PARALLEL_BRANCHES", "F4RES", "OCC5", "WINO4_G48", "DCN_FUSED", "WINO4_X3", "PW_X3"))
+                                    "DW_SPLIT_K", "DW_DEEP_MAX_WGS", "PAIR_BF16", "TUNE_STREAMS", "PARALLEL_BRANCHES", "F4RES", "OCC5", "WINO4_G48", "DCN_FUSED", "WINO4_X3", "PW_X3",
+                                    "DCN_FUSED_BF16"))
 
 
 def conv_pair_eligible(a, b, x, residual=None):
@@ -1363,11 +1364,15 @@ def bsm_compose(height_context, semantic_logits, D, ctx, sem, thr):
 
 
 DCN_FUSED = _os.environ.get("SGV3D_DCN_FUSED", "1") != "0"     # 0: deformable im2col + one GEMM per group (rounds 1-4)
+# bf16 compute mode: the one-launch form of csrc/dcn_fused_bf16.hip.  On: 2.6 - 3.7 x faster than the im2col form in all four cases
+# of tools/dcn_probe.py bf16 (profiles/dcn_bf16_bench.json).  SGV3D_DCN_FUSED_BF16=0 keeps the im2col form in bf16
+# mode only; SGV3D_DCN_FUSED=0 switches it off together with the f32 launch.
+DCN_FUSED_BF16 = _os.environ.get("SGV3D_DCN_FUSED_BF16", "1") != "0"
 
 
 def deform_conv3x3_eligible(x, convs):
     """f32 NHWC input, packed group weights that share one geometry, channels per group a multiple of 32: what
-    sgv3d_deform_conv3x3_forward covers (bf16-activation mode keeps the im2col form)."""
+    sgv3d_deform_conv3x3_forward covers (the bf16 compute mode has a launch of its own: deform_conv3x3_bf16_eligible)."""
     cpg9 = convs[0].cin
     return (DCN_FUSED and not MFMA_BF16 and not MFMA_F32X3 and x.dtype == torch.float32 and len(convs) <= 8 and cpg9 % 9 == 0
             and (cpg9 // 9) % 32 == 0 and convs[0].cout % 4 == 0 and convs[0].k_order == 1
@@ -1395,6 +1400,71 @@ def deform_conv3x3(x, offset, convs, out=None, y_coff=0):
                                                      convs[0].k_pad, convs[0].cout_pad, out.data_ptr(), int(out.shape[-1]), int(y_coff),
                                                      _st(x))
     _lib.check(rc, "sgv3d_deform_conv3x3_forward")
+    return out
+
+
+class PackedDeformBf16:
+    """The weights of a DCNv1 3x3 layer ([cout, cin / groups, 3, 3] f32) rounded once to bf16 and packed in the MFMA-fragment order
+    of csrc/dcn_fused_bf16.hip (sgv3d_deform_conv3x3_bf16_pack_weight), made once per compiled state."""
+
+    def __init__(self, weight, groups, device=None):
+        w = weight.detach()
+        device = device or w.device
+        w = w.to(device=device, dtype=torch.float32).contiguous()
+        cout, cpg, kh, kw = (int(v) for v in w.shape)
+        assert kh == 3 and kw == 3 and cout % int(groups) == 0
+        self.groups, self.channels, self.opg = int(groups), cpg * int(groups), cout // int(groups)
+        lib = _lib.load()
+        nbytes = int(lib.sgv3d_deform_conv3x3_bf16_weight_bytes(self.channels, self.groups, self.opg))
+        if nbytes == 0:
+            raise _lib.SGV3DError(f"deform_conv3x3_bf16: shape not covered (channels={self.channels} groups={self.groups} "
+                                  f"outputs per group={self.opg})")
+        self.w = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=device)
+        with torch.cuda.device(device):
+            rc = lib.sgv3d_deform_conv3x3_bf16_pack_weight(w.data_ptr(), self.channels, self.groups, self.opg, self.w.data_ptr(), _st(w))
+        _lib.check(rc, "sgv3d_deform_conv3x3_bf16_pack_weight")
+        self._keep = w   # the pack kernel reads it asynchronously
+
+
+def deform_conv3x3_bf16_covers(channels, groups, out_channels):
+    """The shapes sgv3d_deform_conv3x3_forward_bf16 covers: at most 8 groups, channels per group a multiple of 32, outputs per
+    group a multiple of 4 (whatever the compute mode: DCN.hip_compile packs the bf16 weights of every covered layer)."""
+    C, g, cout = int(channels), int(groups), int(out_channels)
+    return 0 < g <= 8 and C % g == 0 and (C // g) % 32 == 0 and cout % g == 0 and (cout // g) % 4 == 0
+
+
+def deform_conv3x3_bf16_eligible(x, groups, out_channels):
+    """bf16 compute mode with the one-launch form switched on (DCN_FUSED_BF16), NHWC input in bf16 or f32 and a covered shape
+    (deform_conv3x3_bf16_covers).  SGV3D_DCN_FUSED=0 turns the launch off like the f32 one."""
+    if not (DCN_FUSED and DCN_FUSED_BF16 and MFMA_BF16 and not MFMA_F32X3) or x.dim() != 4 or x.dtype not in (torch.bfloat16, torch.float32):
+        return False
+    return deform_conv3x3_bf16_covers(x.shape[-1], groups, out_channels)
+
+
+def deform_conv3x3_bf16(x, offset, packed, out=None, y_coff=0, out_dtype=None):
+    """DCNv1 forward (lss_fpn.py:190-198) in one launch on the bf16 matrix cores: x NHWC [B,H,W,C] bf16 or f32, offset f32
+    [B,H,W,>=18], ``packed`` a PackedDeformBf16.  Writes out[..., y_coff : y_coff + groups * opg] (f32 or bf16; default: the dtype
+    of x); the bf16 output is the f32 one rounded once."""
+    B, H, W, C = (int(v) for v in x.shape)
+    g, opg = packed.groups, packed.opg
+    assert C == packed.channels and x.dtype in (torch.bfloat16, torch.float32)
+    assert x.is_contiguous() and offset.is_contiguous() and offset.dtype == torch.float32 and int(offset.shape[-1]) >= 18
+    assert tuple(offset.shape[:3]) == (B, H, W)
+    if out is None:
+        out = torch.empty(B, H, W, g * opg, dtype=out_dtype or x.dtype, device=x.device)
+    assert out.is_contiguous() and out.dtype in (torch.bfloat16, torch.float32) and tuple(out.shape[:3]) == (B, H, W)
+    assert out_dtype is None or out.dtype == out_dtype
+    flops = 2.0 * B * H * W * g * opg * 9 * (C // g)
+    nbytes = (float(B * H * W) * (C * x.element_size() + 18 * 4 + g * opg * out.element_size()) + 2.0 * g * opg * 9 * (C // g))
+    # (no ``symbol`` extra: none of the bf16-mode launches records one, and bench.py then lets the dominant LABEL stand for its
+    #  kernel -- a single symbol here would make this launch the "dominant kernel" of every --dtype bf16 roofline pass.  The label
+    #  is one instantiation family, dcn3x3_fused_bf16_kernel, priced with these flops against the bf16 peak.)
+    with torch.cuda.device(x.device), prof("conv_dcn_fused_bf16", flops, nbytes):
+        rc = _lib.load().sgv3d_deform_conv3x3_forward_bf16(B, H, W, C, g, opg, x.data_ptr(), int(x.dtype == torch.bfloat16),
+                                                          offset.data_ptr(), int(offset.shape[-1]), packed.w.data_ptr(),
+                                                          out.data_ptr(), int(out.dtype == torch.bfloat16), int(out.shape[-1]),
+                                                          int(y_coff), _st(x))
+    _lib.check(rc, "sgv3d_deform_conv3x3_forward_bf16")
     return out
 
 

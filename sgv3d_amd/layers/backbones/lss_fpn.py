@@ -157,7 +157,8 @@ class DCN(HipModule):
     """mmcv 1.4.0 ``DeformConv2dPack`` as configured at lss_fpn.py:190-198 (3x3, pad 1, groups 4,
     deform_groups 1, no bias): ``conv_offset`` (zero-initialised 3x3 conv, 18 channels) predicts the
     sampling offsets; the deformable convolution itself is one implicit GEMM whose A operand is sampled on the fly
-    (``hip_ops.deform_conv3x3``; bf16-activation mode: a deformable bilinear im2col feeds one GEMM per group)."""
+    (``hip_ops.deform_conv3x3`` on the f32 matrix cores; in bf16 compute mode ``hip_ops.deform_conv3x3_bf16``
+    with bf16 or f32 tensors, switch ``hip_ops.DCN_FUSED_BF16``).  ``SGV3D_DCN_FUSED=0``, or a shape neither launch covers: a deformable bilinear im2col feeds one GEMM per group."""
 
     def __init__(self, in_channels, out_channels, kernel_size=3, padding=1, groups=1, deform_groups=1,
                  stride=1, dilation=1, im2col_step=32, **unused):
@@ -179,7 +180,12 @@ class DCN(HipModule):
             wg = self.weight.detach()[gi * opg:(gi + 1) * opg]                   # [opg, cpg, 3, 3]
             wg = wg.permute(0, 2, 3, 1).reshape(opg, 9 * cpg, 1, 1).contiguous()   # k = (tap, c)
             convs.append(PackedConv(wg, device=device))
-        return dict(offset=conv_bn(self.conv_offset, None, False, device), convs=convs, opg=opg, cpg=cpg)
+        # the fragment-ordered bf16 weights of the bf16 mode's one-launch form (147 KB per 128 x 128 group), packed with every compiled
+        # state of a covered shape whatever the mode it was compiled in -- never inside a forward; hip_invalidate drops them with the rest
+        dcn_bf16 = None
+        if hip_ops.deform_conv3x3_bf16_covers(self.in_channels, g, self.out_channels):
+            dcn_bf16 = hip_ops.PackedDeformBf16(self.weight, g, device=device)
+        return dict(offset=conv_bn(self.conv_offset, None, False, device), convs=convs, opg=opg, cpg=cpg, dcn_bf16=dcn_bf16)
 
     def hip_forward(self, x):
         s = self.hip_state(x.device)
@@ -188,6 +194,9 @@ class DCN(HipModule):
         if hip_ops.deform_conv3x3_eligible(x, s['convs']):
             # one launch: the bilinear samples go straight into the GEMM's LDS stage (csrc/dcn_fused.hip), no column tensor
             return hip_ops.deform_conv3x3(x, offset, s['convs'])
+        if s['dcn_bf16'] is not None and hip_ops.deform_conv3x3_bf16_eligible(x, self.groups, self.out_channels):
+            # bf16 mode, one launch (csrc/dcn_fused_bf16.hip): same operand bits as the im2col form below, no column tensor
+            return hip_ops.deform_conv3x3_bf16(x, offset, s['dcn_bf16'])
         col = hip_ops.deform_im2col3x3(x, offset, self.groups)      # [B,H,W,g*9*cpg], dtype of x
         out = torch.empty(B, H, W, self.out_channels, dtype=x.dtype, device=x.device)
         for gi, conv in enumerate(s['convs']):
