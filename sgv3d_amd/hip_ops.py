@@ -5,11 +5,15 @@ Tensors here are torch CUDA tensors used purely as device buffers: activations a
 current stream.  No arithmetic happens in PyTorch on this path.
 """
 import ctypes
+from collections import namedtuple
+from functools import partialmethod
 
 import torch
 
-from . import _lib, pack_cache
+from . import _lib, conv_tiles, pack_cache
 from ._lib import ConvDesc, CONV_NORMAL, CONV_DECONV, CONV_NCHW_OUT, CONV_GROUP_PLANES  # noqa: F401
+from .conv_tiles import (TILE_WINO, TILE_WINO_RES, TILE_PATCH, TILE_WINO_HALF, TILE_WINO4, TILE_WINO4_WIDE, TILE_WINO4_NARROW,  # noqa: F401
+                         TILE_WINO4_OCC, TILE_WINO4_G48, TILE_F4RES)
 
 
 def _st(t):
@@ -156,68 +160,38 @@ def _is_gfx950(device):
 
 load_default_tune_dbs()
 load_tune_db()
-TILE_NAMES = {1: "128x128", 2: "128x64", 3: "64x128", 4: "64x64", 5: "wino", 6: "wino_resident", 7: "patch_bf16", 8: "wino_half",
-              9: "wino4", 10: "wino4", 15: "wino4",                         # F(4x4,3x3) with the 64x64 / 64x128 / 32x128 GEMM tile
-              11: "128x128", 12: "128x64", 13: "64x128", 14: "64x64",      # 11..14: f32x3 of tiles 1..4 (host-side ids)
-              21: "128x128", 22: "128x64", 23: "64x128", 24: "64x64",      # 21..24: tiles 1..4 walked m-tile first (SGV3D_TILE_MFIRST)
-              31: "dw_bf16", 32: "dw_bf16", 33: "dw_bf16", 34: "dw_bf16", 35: "dw_bf16",   # bf16 direct-weight kernel (SGV3D_TILE_DW_*)
-              36: "dw_bf16", 37: "dw_bf16",                                                # ... requests two k-chunks ahead (*_DEEP)
-              38: "dw_bf16", 39: "dw_bf16",                                                # ... 64 pixels x 128 channels (39: two chunks ahead)
-              40: "wino4_resident",    # F(4x4,3x3) with the transformed input resident in LDS (sgv3d_conv3x3_f4res_forward)
-              47: "wino4",
-              50: "wino4_x3", 51: "wino4_x3", 52: "wino4_x3", 53: "wino4_x3", 54: "wino4_x3",    # F(4x4) with the f32x3 position GEMM
-              55: "wino4_x3", 56: "wino4_x3", 57: "wino4_x3", 58: "wino4_x3", 59: "wino4_x3",    # (csrc/gemm_x3_grouped.hip), by tile shape
-              60: "pw_x3", 61: "pw_x3", 62: "pw_x3", 64: "pw_x3", 65: "pw_x3", 66: "pw_x3",      # pointwise f32x3 (csrc/conv_pw_x3.hip)
-              70: "pw_x3", 71: "pw_x3", 72: "pw_x3", 74: "pw_x3", 75: "pw_x3", 76: "pw_x3",      # ... walked m-tile first
-              80: "pw_x3", 81: "pw_x3", 82: "pw_x3", 90: "pw_x3", 91: "pw_x3", 92: "pw_x3",      # ... 256 channels per workgroup
-              44: "64x64", 45: "64x64",    # the 64x64 tile at five workgroups per CU (SGV3D_TILE_OCC5); 45: walked m-tile first
-              46: "wino4"}                 # F(4x4,3x3) in three launches with the five-per-CU 64x64 GEMM tile
+# Host tile ids: what every id means -- family, ABI code, workgroup footprint, weight form, split-K policy, profile symbol -- is ONE
+# table, sgv3d_amd/conv_tiles.py; the names below are read from it
+TILES = conv_tiles.TILES
+TILE_NAMES = {t: T.label for t, T in TILES.items()}
 MFIRST = _os.environ.get("SGV3D_MFIRST", "1") != "0"
-TILE_WINO = 5       # host-side algorithm id: sgv3d_conv2d_winograd_forward instead of the implicit GEMM
-TILE_WINO_RES = 6   # = SGV3D_WINOGRAD_RESIDENT: its patch-resident variant (cin <= 96, many cout tiles)
-TILE_PATCH = 7      # bf16 mode: the LDS-resident-patch 3x3 kernel (sgv3d_conv3x3_patch_bf16_forward)
-TILE_WINO_HALF = 8  # = SGV3D_WINOGRAD_HALF: 64 tiles x 32 channels per workgroup, positions split over wave pairs (2 workgroups / CU)
-TILE_WINO4 = 9      # Winograd F(4x4,3x3) in three launches (sgv3d_conv2d_winograd4_forward), GEMM tile 64x64; 10: 64x128
-TILE_WINO4_WIDE = 10
-TILE_WINO4_NARROW = 15   # ... with the 32x128 GEMM tile: rows per position padded to 32 instead of 64 (336 tiles -> 352, 84 -> 96)
-TILE_WINO4_OCC = 46      # ... with the five-workgroups-per-CU form of the 64x64 GEMM tile (SGV3D_TILE_64x64 | SGV3D_TILE_OCC5)
-TILE_WINO4_G48 = 47      # ... with the grouped GEMM on v_mfma_f32_16x16x4_f32, 48 x 64 tiles (SGV3D_TILE_48x64): rows padded to 48 (336 -> 336)
-# ... with the position GEMM on the bf16 matrix cores, f32-accurate ("f32x3": every operand split exactly into three bf16 terms by its
-# PRODUCER -- the weight packer, the input transform --, six partial products accumulated in f32; csrc/gemm_x3_grouped.hip).  Host ids
-# 50 + v: v % 5 = m-tile of {48, 64, 96, 112, 128} rows, v >= 5: 160 instead of 128 columns per workgroup.
-WINO4_X3_TILES = tuple(range(50, 60))
-X3_TILE_ROWS = {50 + v: (48, 64, 96, 112, 128)[v % 5] for v in range(10)}
-X3_TILE_COLS = {50 + v: 160 if v >= 5 else 128 for v in range(10)}
-WINO4_TILES = (TILE_WINO4, TILE_WINO4_WIDE, TILE_WINO4_NARROW, TILE_WINO4_OCC, TILE_WINO4_G48) + WINO4_X3_TILES
+# F(4x4) with the f32x3 position GEMM (csrc/gemm_x3_grouped.hip), by tile shape
+WINO4_X3_TILES = conv_tiles.family("wino4_x3")
+X3_TILE_ROWS = {t: TILES[t].bm for t in WINO4_X3_TILES}
+X3_TILE_COLS = {t: TILES[t].bn for t in WINO4_X3_TILES}
+WINO4_TILES = conv_tiles.family("wino4", "wino4_x3")
 WINO4_G48 = _os.environ.get("SGV3D_WINO4_G48", "1") != "0"     # 0: never a candidate
 # 0: the f32x3 position GEMM is never a candidate -- every product of the f32 path on the f32 MFMA (bench.py's native_f32_value)
 WINO4_X3 = _os.environ.get("SGV3D_WINO4_X3", "1") != "0"
 # Implicit-GEMM layers (1x1, strided 3x3 / 1x1, patchify: at most 32 taps, cin % 32 == 0) with f32-accurate products on the bf16 matrix
-# cores (csrc/conv_pw_x3.hip: weights split into three
-# bf16 terms by the packer, activations on their way into LDS).  Host ids 60 + v / 70 + v (m-tile first): v & 3 = {0: 32, 1: 64, 2: 128}
-# pixels per workgroup, v & 4: 64 instead of 128 channels.  0: never a candidate.
+# cores (csrc/conv_pw_x3.hip).  0: never a candidate.
 PW_X3 = _os.environ.get("SGV3D_PW_X3", "1") != "0"
-PW_X3_TILES = (60, 61, 62, 64, 65, 66, 70, 71, 72, 74, 75, 76, 80, 81, 82, 90, 91, 92)    # 8x / 9x: 256 channels per workgroup (8 waves)
-PW_X3_DIMS = {t: (32 << ((t % 10) & 3), 256 if t >= 80 else 64 if (t % 10) & 4 else 128) for t in PW_X3_TILES}
-# F(4x4,3x3) in ONE launch with V = B^T d B of a 16x16 block resident in LDS (csrc/head_wino4.hip: conv_f4res_kernel): 3x3 /
-# stride 1 / pad 1 layers with 64 input channels (ResNet layer 1) or 64 output channels (the CenterHead's shared layer), f32
-TILE_F4RES = 40
+PW_X3_TILES = conv_tiles.family("pw_x3")
+PW_X3_DIMS = {t: (TILES[t].bm, TILES[t].bn) for t in PW_X3_TILES}
+# F(4x4,3x3) in ONE launch (TILE_F4RES): 3x3 / stride 1 / pad 1 layers with 64 input channels (ResNet layer 1) or 64 output channels
+# (the CenterHead's shared layer), f32
 F4RES = _os.environ.get("SGV3D_F4RES", "1") != "0"     # 0: never a candidate
 # f32 implicit GEMM, 64x64 tile with five workgroups per CU (32 KB of swizzled LDS, one register stage; csrc/conv_igemm.hip:
-# OCC): for the small-K layers; host ids 44 / 45 (= m-tile first) -> SGV3D_TILE_64x64 | SGV3D_TILE_OCC5 [| SGV3D_TILE_MFIRST]
-OCC5_TILES = (44, 45)
+# OCC): for the small-K layers
+OCC5_TILES = conv_tiles.select("igemm", occ5=True) + conv_tiles.select("igemm", occ5=True, mfirst=True)
 OCC5 = _os.environ.get("SGV3D_OCC5", "1") != "0"       # 0: never candidates
 WINO4 = _os.environ.get("SGV3D_WINO4", "1") != "0"     # 0: F(4x4) is never a candidate
 WINO4_MIN_CHANNELS = 128                              # candidates only where cin and cout are at least this
 WINO_HALF = _os.environ.get("SGV3D_WINO_HALF", "1") != "0"
 PATCH_BF16 = _os.environ.get("SGV3D_PATCH_BF16", "1") != "0"
-# = SGV3D_TILE_DW_*: bf16 mode, bf16 tensors in and out: the direct-weight implicit GEMM (sgv3d_conv_dw_bf16_forward), pixels x
-# channels per workgroup 64x256 / 128x128 / 256x64 (64 pixels per wave) and 128x256 / 256x128 (128 pixels per wave)
-# 36 / 37 = SGV3D_TILE_DW_64x256_DEEP / 128x128_DEEP: rows and fragments requested two k-chunks ahead (launches of about one
-# workgroup per CU, where nothing else hides the memory round trips); no split-K
-# 38 = SGV3D_TILE_DW_64x128: one 32-channel tile per wave -- twice the workgroups of 64x256 on small maps; 39: its *_DEEP form
-DW_TILES = (31, 32, 33, 34, 35, 36, 37, 38, 39)
-DW_DEEP_TILES = (36, 37, 39)
+# bf16 mode, bf16 tensors in and out: the direct-weight implicit GEMM (sgv3d_conv_dw_bf16_forward)
+DW_TILES = conv_tiles.family("dw_bf16")
+DW_DEEP_TILES = conv_tiles.select("dw_bf16", deep=True)
 DW_DEEP = _os.environ.get("SGV3D_DW_DEEP", "1") != "0"   # 0: the *_DEEP tiles are never candidates
 DW_NARROW = _os.environ.get("SGV3D_DW_NARROW", "1") != "0"   # 0: the 64x128 tile is never a candidate
 DW_DEEP_MAX_WGS = int(_os.environ.get("SGV3D_DW_DEEP_MAX_WGS", "768"))   # the *_DEEP tiles are candidates for grids up to this many workgroups
@@ -253,7 +227,8 @@ class prof:
 def heuristic_tile(M, N):
     """Same cost model as pick_tile() in csrc/conv_igemm.hip."""
     best, best_cost = 1, None
-    for t, (bm, bn, pen) in enumerate(((128, 128, 1.0), (128, 64, 1.06), (64, 128, 1.06), (64, 64, 1.18)), 1):
+    for t, pen in zip(conv_tiles.select("igemm"), (1.0, 1.06, 1.06, 1.18)):
+        bm, bn = TILES[t].bm, TILES[t].bn
         tiles = -(-M // bm) * -(-N // bn)
         cost = -(-tiles // 256) * bm * bn * pen
         if best_cost is None or cost < best_cost:
@@ -298,6 +273,84 @@ def channel_align():
 def pad_channels(c, align=None):
     align = int(align or channel_align())
     return (int(c) + align - 1) // align * align
+
+
+# The packed forms of a layer's weights: attribute, packer (called as packer(source, *before, form, *after, stream)), whether the form
+# is a permutation of the parameter with padding / rounding (what the pack cache can refresh by a gather), and the plan: (source tensor,
+# form buffer, before, after, {what the launch needs to know about the form}), or None for a layer that has no such form.
+_Form = namedtuple("_Form", "attr packer permutation plan")
+_F32, _BF16, _U8 = torch.float32, torch.bfloat16, torch.uint8
+_up32 = lambda v: (v + 31) // 32 * 32
+
+
+def _plan_w(pc, lib):
+    src = pc._keep
+    odim = 1 if pc.transposed else 0
+    cout, cin = int(src.shape[odim]), int(src.shape[1 - odim])
+    if (ALIAS_1X1_WEIGHTS and not pc.transposed and pc.kh == 1 and pc.kw == 1 and cout == pc.cout_pad and cin == pc.k_pad
+            and pc.cin == cin and src.is_contiguous() and src.data_ptr() % 16 == 0):
+        # a 1x1 layer whose channel counts need no padding: OIHW [cout, cin, 1, 1] IS the packed layout [cout_pad, k_pad] (one tap:
+        # both k orders are the identity) -- no pack launch (a training step repacks every layer's weights, forward and data
+        # gradient, at ~5 us per launch)
+        return src, src.view(pc.cout_pad, pc.k_pad), None, None, {}
+    return (src, torch.empty(pc.cout_pad, pc.k_pad, dtype=_F32, device=src.device),
+            (cout, cin, int(src.shape[2]), int(src.shape[3]), pc.cin, 1 if pc.transposed else 0, pc.k_order), (pc.k_pad, pc.cout_pad), {})
+
+
+def _plan_w_wino4(pc, lib):
+    # U[p] = (G g G^T)[i][j] for the 36 positions of F(4x4,3x3), each a packed 1x1 weight block of the implicit-GEMM kernel
+    k_pad, cout_pad = pack_geometry(pc.cin, pc.cout)
+    return (pc._keep, torch.empty(36, cout_pad, k_pad, dtype=_F32, device=pc._keep.device),
+            (pc.cout, int(pc._keep.shape[1]), k_pad, cout_pad), (), {"wino4_geom": (k_pad, cout_pad)})
+
+
+def _plan_w_pw_x3(pc, lib):
+    # three bf16 planes per element in fragment order: [cout_pad / 16][kh kw cin / 32][3][512], cout_pad = cout rounded up to 32
+    cout_pad = _up32(pc.cout)
+    return (pc._keep, torch.empty(cout_pad // 16, _up32(pc.kh * pc.kw * pc.cin) // 32, 3, 512, dtype=_BF16, device=pc._keep.device),
+            (pc.cout, int(pc._keep.shape[1]), pc.kh, pc.kw, pc.cin, cout_pad), (), {"pw_x3_cout_pad": cout_pad})
+
+
+def _plan_w_wino4_x3(pc, lib):
+    # U[p] of F(4x4,3x3) as three bf16 planes per element: [36][cout_pad][cin / 32][3][32], cout_pad = cout rounded up to 32
+    cout_pad = _up32(pc.cout)
+    return (pc._keep, torch.empty(36, cout_pad, pc.cin // 32, 3, 32, dtype=_BF16, device=pc._keep.device),
+            (pc.cout, int(pc._keep.shape[1]), pc.cin, cout_pad), (), {"wino4_x3_cout_pad": cout_pad})
+
+
+def _plan_w_dw(pc, lib):
+    # transposed convolution (kernel == stride): a 1x1 layer with ks * ks * cout outputs ordered (dy, dx, co)
+    w, n = pc._keep, pc.cout                  # [cout, cin_real, kh, kw] f32 on the device ([cin_real, cout, ks, ks] transposed)
+    if pc.transposed:
+        n = pc.ks * pc.ks * pc.cout
+        w = w.permute(2, 3, 1, 0).reshape(n, int(w.shape[0]), 1, 1).contiguous()
+    return (w, torch.empty(lib.sgv3d_conv_dw_bf16_weight_bytes(n, pc.cin, pc.kh, pc.kw), dtype=_U8, device=w.device),
+            (n, int(w.shape[1]), pc.cin, pc.kh, pc.kw), (), {"_keep_dw": w})      # (the packer reads ``w`` asynchronously)
+
+
+_FORMS = {
+    # implicit GEMM: [cout_pad, k_pad] f32
+    "w": _Form("_w", "sgv3d_conv_pack_weight", True, _plan_w),
+    # ... its bf16 copy (bf16-activation launches)
+    "w_bf16": _Form("w_bf16", "sgv3d_conv_weight_to_bf16", True, lambda pc, lib: (
+        pc.w, torch.empty(pc.cout_pad, pc.k_pad, dtype=_BF16, device=pc._keep.device), (pc.k_pad, pc.cout_pad), (), {})),
+    # Winograd F(2x2,3x3)
+    "w_wino": _Form("_w_wino", "sgv3d_conv_winograd_pack_weight", False, lambda pc, lib: pc.wino_ok and (
+        pc._keep, torch.empty(lib.sgv3d_conv_winograd_weight_floats(pc.cout, pc.cin), dtype=_F32, device=pc._keep.device),
+        (pc.cout, int(pc._keep.shape[1]), pc.cin), (), {})),
+    # U = G g G^T in the fragment order conv_f4res_kernel streams
+    "w_f4res": _Form("w_f4res", "sgv3d_conv3x3_f4res_pack_weight", False, lambda pc, lib: (
+        pc._keep, torch.empty(int(lib.sgv3d_conv3x3_f4res_weight_floats(pc.cout, pc.cin)), dtype=_F32, device=pc._keep.device),
+        (pc.cout, int(pc._keep.shape[1]), pc.cin), (), {})),
+    "w_wino4": _Form("w_wino4", "sgv3d_conv_winograd4_pack_weight", False, _plan_w_wino4),
+    "w_pw_x3": _Form("w_pw_x3", "sgv3d_conv_pack_weight_x3", False, _plan_w_pw_x3),
+    "w_wino4_x3": _Form("w_wino4_x3", "sgv3d_conv_winograd4_pack_weight_x3", False, _plan_w_wino4_x3),
+    # fragment-ordered bf16 weights of the direct-weight kernel / of the patch kernel
+    "w_dw": _Form("w_dw", "sgv3d_conv_dw_bf16_pack_weight", True, _plan_w_dw),
+    "w_patch": _Form("w_patch", "sgv3d_conv3x3_patch_bf16_pack_weight", True, lambda pc, lib: (
+        pc._keep, torch.empty(lib.sgv3d_conv3x3_patch_bf16_weight_bytes(pc.cout, pc.cin), dtype=_U8, device=pc._keep.device),
+        (pc.cout, pc.cin), (), {})),
+}
 
 
 class PackedConv:
@@ -355,7 +408,9 @@ class PackedConv:
         # Every packed form of the weights (implicit GEMM, F(2x2) / F(4x4) Winograd, bf16 patch / direct-weight) is made on
         # first use: a training step packs the current weights of every layer twice (forward, data gradient) and only
         # needs the form its kernel choice reads.
-        self._w = self._w_wino = None
+        # (the attributes of _FORMS, and what their packers note down for the launch)
+        self._w = self._w_wino = self.w_bf16 = self.w_f4res = self.w_wino4 = self.w_pw_x3 = self.w_wino4_x3 = self.w_dw = self.w_patch = None
+        self.wino4_geom = self.pw_x3_cout_pad = self.wino4_x3_cout_pad = self._keep_dw = None
         self._entry = None          # pack_cache._Entry when this object is kept across training steps (sgv3d_amd/pack_cache.py)
         self.device = device
         # Winograd F(2x2,3x3) covers the layer
@@ -363,66 +418,42 @@ class PackedConv:
                             and self.pad == 1 and self.cin % 8 == 0)
         self._keep = w  # the pack kernels read it asynchronously
         self._tile_cache = {}
-        # bf16 mode: fragment-ordered bf16 weights for the patch kernel, packed on first use
-        self.w_patch = None
-        self.w_bf16 = None
         self.patch_ok = (not transposed and kh == 3 and kw == 3 and self.stride == 1 and self.dil == 1
                          and self.pad == 1 and self.cin % 32 == 0 and self.cout % 8 == 0 and self.cin == cin)
 
-    @property
-    def w(self):
-        """Weights packed for the implicit-GEMM kernels (sgv3d_conv_pack_weight), [cout_pad, k_pad] f32."""
-        if self._w is None:
-            src = self._keep
-            odim = 1 if self.transposed else 0
-            cout, cin = int(src.shape[odim]), int(src.shape[1 - odim])
-            if (ALIAS_1X1_WEIGHTS and not self.transposed and self.kh == 1 and self.kw == 1 and cout == self.cout_pad and cin == self.k_pad
-                    and self.cin == cin and src.is_contiguous() and src.data_ptr() % 16 == 0):
-                # a 1x1 layer whose channel counts need no padding: OIHW [cout, cin, 1, 1] IS the packed layout [cout_pad, k_pad] (one tap:
-                # both k orders are the identity) -- no pack launch (a training step repacks every layer's weights, forward and data
-                # gradient, at ~5 us per launch)
-                self._w = src.view(self.cout_pad, self.k_pad)
-                if self._entry is not None and src.data_ptr() != self._entry.param.data_ptr():
-                    # kept across steps and NOT a view of the parameter itself (the rotated copy of a data gradient): refreshed like a
-                    # packed form, in place
-                    self._entry.register('w', self._w, lambda pc: pc.w)
-                return self._w
-            self._w = torch.empty(self.cout_pad, self.k_pad, dtype=torch.float32, device=self.device)
-            with torch.cuda.device(self.device):
-                rc = _lib.load().sgv3d_conv_pack_weight(src.data_ptr(), cout, cin, int(src.shape[2]), int(src.shape[3]), self.cin,
-                                                       1 if self.transposed else 0, self.k_order, self._w.data_ptr(),
-                                                       self.k_pad, self.cout_pad, _st(src))
-            _lib.check(rc, "sgv3d_conv_pack_weight")
-            if self._entry is not None:
-                self._entry.register('w', self._w, lambda pc: pc.w)
-        return self._w
+    def _form(self, name):
+        """The packed weight form ``name`` of _FORMS, made on first use by its packer.  Bound to a pack-cache entry, a form that is a
+        permutation of the parameter registers with it (refreshed in place from then on); one that is not makes the layer leave the
+        cache (pack_cache._Entry.call)."""
+        f = _FORMS[name]
+        if self._entry is not None and not f.permutation:
+            raise pack_cache.NotAPermutation(name)     # a transformed form: this layer packs per call
+        buf = getattr(self, f.attr)
+        if buf is not None:
+            return buf
+        lib = _lib.load()
+        plan = f.plan(self, lib)
+        if not plan:
+            return None
+        src, buf, before, after, notes = plan
+        if before is not None:                  # (None: ``buf`` is a view of ``src``, nothing to launch)
+            with torch.cuda.device(src.device):
+                rc = getattr(lib, f.packer)(src.data_ptr(), *before, buf.data_ptr(), *after, _st(src))
+            _lib.check(rc, f.packer)
+        setattr(self, f.attr, buf)
+        for k, v in notes.items():
+            setattr(self, k, v)
+        # kept across steps: refreshed in place from the parameter -- unless it is a view of the parameter itself
+        if self._entry is not None and (before is not None or src.data_ptr() != self._entry.param.data_ptr()):
+            self._entry.register(name, buf, lambda pc: pc._form(name))
+        return buf
 
-    @property
-    def w_wino(self):
-        """Winograd F(2x2,3x3) weights (sgv3d_conv_winograd_pack_weight), None when the layer is not covered."""
-        if self._entry is not None:
-            raise pack_cache.NotAPermutation('w_wino')     # a transformed form: this layer packs per call (pack_cache._Entry.call)
-        if self._w_wino is None and self.wino_ok:
-            lib = _lib.load()
-            src = self._keep
-            self._w_wino = torch.empty(lib.sgv3d_conv_winograd_weight_floats(self.cout, self.cin), dtype=torch.float32,
-                                       device=self.device)
-            with torch.cuda.device(self.device):
-                rc = lib.sgv3d_conv_winograd_pack_weight(src.data_ptr(), self.cout, int(src.shape[1]), self.cin,
-                                                         self._w_wino.data_ptr(), _st(src))
-            _lib.check(rc, "sgv3d_conv_winograd_pack_weight")
-        return self._w_wino
+    w = property(lambda self: self._form('w'), doc="weights packed for the implicit-GEMM kernels, [cout_pad, k_pad] f32")
+    w_wino = property(lambda self: self._form('w_wino'), doc="Winograd F(2x2,3x3) weights, None when the layer is not covered")
 
-    def _bf16_weights(self):
-        """bf16 copy of the packed implicit-GEMM weights (bf16-activation launches), made on first use."""
-        if self.w_bf16 is None:
-            self.w_bf16 = torch.empty(self.cout_pad, self.k_pad, dtype=torch.bfloat16, device=self.device)
-            with torch.cuda.device(self.device):
-                rc = _lib.load().sgv3d_conv_weight_to_bf16(self.w.data_ptr(), self.k_pad, self.cout_pad, self.w_bf16.data_ptr(), _st(self.w))
-            _lib.check(rc, "sgv3d_conv_weight_to_bf16")
-            if self._entry is not None:
-                self._entry.register('w_bf16', self.w_bf16, lambda pc: pc._bf16_weights())
-        return self.w_bf16
+    _bf16_weights = partialmethod(_form, 'w_bf16')
+    _dw_weights = partialmethod(_form, 'w_dw')
+    _patch_weights = partialmethod(_form, 'w_patch')
 
     def wino4_ok(self, d=None, gate=None):
         """F(4x4,3x3) covers this layer (and launch): 3x3 / stride 1 / pad 1, f32, NHWC output, no gate, many channels."""
@@ -447,38 +478,6 @@ class PackedConv:
                   and d.res_ld % 4 == 0)
         return ok
 
-    def _f4res_weights(self):
-        """U = G g G^T in the fragment order conv_f4res_kernel streams (sgv3d_conv3x3_f4res_pack_weight), made on first use."""
-        if self._entry is not None:
-            raise pack_cache.NotAPermutation('w_f4res')     # a transformed form: this layer packs per call (pack_cache._Entry.call)
-        if getattr(self, 'w_f4res', None) is None:
-            lib = _lib.load()
-            w = self._keep                                           # [cout, cin_real, 3, 3] f32 on the device
-            self.w_f4res = torch.empty(int(lib.sgv3d_conv3x3_f4res_weight_floats(self.cout, self.cin)), dtype=torch.float32,
-                                       device=w.device)
-            with torch.cuda.device(w.device):
-                rc = lib.sgv3d_conv3x3_f4res_pack_weight(w.data_ptr(), self.cout, int(w.shape[1]), self.cin,
-                                                         self.w_f4res.data_ptr(), _st(w))
-            _lib.check(rc, "sgv3d_conv3x3_f4res_pack_weight")
-        return self.w_f4res
-
-    def _wino4_weights(self):
-        """U[p] = (G g G^T)[i][j] for the 36 positions of F(4x4,3x3), each a packed 1x1 weight block of the implicit-GEMM
-        kernel (36 x cout_pad x k_pad floats), made on first use by one kernel (sgv3d_conv_winograd4_pack_weight)."""
-        if self._entry is not None:
-            raise pack_cache.NotAPermutation('w_wino4')     # a transformed form: this layer packs per call (pack_cache._Entry.call)
-        if getattr(self, 'w_wino4', None) is None:
-            lib = _lib.load()
-            w = self._keep                                           # [cout, cin_real, 3, 3] f32 on the device
-            k_pad, cout_pad = pack_geometry(self.cin, self.cout)
-            packed = torch.empty(36, cout_pad, k_pad, dtype=torch.float32, device=w.device)
-            with torch.cuda.device(w.device):
-                rc = lib.sgv3d_conv_winograd4_pack_weight(w.data_ptr(), self.cout, int(w.shape[1]), k_pad, cout_pad,
-                                                          packed.data_ptr(), _st(w))
-            _lib.check(rc, "sgv3d_conv_winograd4_pack_weight")
-            self.w_wino4, self.wino4_geom = packed, (k_pad, cout_pad)
-        return self.w_wino4
-
     def pw_x3_ok(self, d=None, gate=None, io=0):
         """The implicit-GEMM f32x3 kernel (csrc/conv_pw_x3.hip) covers this layer (and launch): a convolution with at most 32 taps and
         cin % 32 == 0 -- the 1x1 layers, the strided 3x3 / 1x1 layers between the stages, the patchify layers of the necks -- or, with
@@ -493,78 +492,10 @@ class PackedConv:
                   and d.res_ld % 4 == 0)
         return ok
 
-    def _pw_x3_weights(self):
-        """The weights as three bf16 planes per element in fragment order ([cout_pad / 16][kh kw cin / 32][3][512], cout_pad = cout
-        rounded up to 32), made on first use (sgv3d_conv_pack_weight_x3)."""
-        if self._entry is not None:
-            raise pack_cache.NotAPermutation('w_pw_x3')     # a transformed form: this layer packs per call (pack_cache._Entry.call)
-        if getattr(self, 'w_pw_x3', None) is None:
-            lib = _lib.load()
-            w = self._keep                                           # [cout, cin_real, kh, kw] f32 on the device
-            cout_pad = (self.cout + 31) // 32 * 32
-            k_pad = (self.kh * self.kw * self.cin + 31) // 32 * 32
-            packed = torch.empty(cout_pad // 16, k_pad // 32, 3, 512, dtype=torch.bfloat16, device=w.device)
-            with torch.cuda.device(w.device):
-                rc = lib.sgv3d_conv_pack_weight_x3(w.data_ptr(), self.cout, int(w.shape[1]), self.kh, self.kw, self.cin, cout_pad,
-                                                   packed.data_ptr(), _st(w))
-            _lib.check(rc, "sgv3d_conv_pack_weight_x3")
-            self.w_pw_x3, self.pw_x3_cout_pad = packed, cout_pad
-        return self.w_pw_x3
-
-    def _wino4_x3_weights(self):
-        """U[p] of F(4x4,3x3) as three bf16 planes per element ([36][cout_pad][cin / 32][3][32], cout_pad = cout rounded up to 32) for
-        the f32x3 position GEMM, made on first use by one kernel (sgv3d_conv_winograd4_pack_weight_x3)."""
-        if self._entry is not None:
-            raise pack_cache.NotAPermutation('w_wino4_x3')     # a transformed form: this layer packs per call (pack_cache._Entry.call)
-        if getattr(self, 'w_wino4_x3', None) is None:
-            lib = _lib.load()
-            w = self._keep                                           # [cout, cin_real, 3, 3] f32 on the device
-            cout_pad = (self.cout + 31) // 32 * 32
-            packed = torch.empty(36, cout_pad, self.cin // 32, 3, 32, dtype=torch.bfloat16, device=w.device)
-            with torch.cuda.device(w.device):
-                rc = lib.sgv3d_conv_winograd4_pack_weight_x3(w.data_ptr(), self.cout, int(w.shape[1]), self.cin, cout_pad,
-                                                             packed.data_ptr(), _st(w))
-            _lib.check(rc, "sgv3d_conv_winograd4_pack_weight_x3")
-            self.w_wino4_x3, self.wino4_x3_cout_pad = packed, cout_pad
-        return self.w_wino4_x3
-
-    def _dw_weights(self):
-        """Fragment-ordered bf16 weights of the direct-weight kernel (sgv3d_conv_dw_bf16_pack_weight), made on first use.
-        Transposed convolution (kernel == stride): a 1x1 layer with ks * ks * cout outputs ordered (dy, dx, co)."""
-        if getattr(self, 'w_dw', None) is None:
-            lib = _lib.load()
-            w = self._keep                                           # [cout, cin_real, kh, kw] f32 on the device ([cin_real, cout, ks, ks] transposed)
-            n = self.cout
-            if self.transposed:
-                w = w.permute(2, 3, 1, 0).reshape(self.ks * self.ks * self.cout, int(w.shape[0]), 1, 1).contiguous()
-                n = self.ks * self.ks * self.cout
-            self.w_dw = torch.empty(lib.sgv3d_conv_dw_bf16_weight_bytes(n, self.cin, self.kh, self.kw), dtype=torch.uint8, device=w.device)
-            with torch.cuda.device(w.device):
-                rc = lib.sgv3d_conv_dw_bf16_pack_weight(w.data_ptr(), n, int(w.shape[1]), self.cin, self.kh, self.kw,
-                                                        self.w_dw.data_ptr(), _st(w))
-            _lib.check(rc, "sgv3d_conv_dw_bf16_pack_weight")
-            self._keep_dw = w
-            if self._entry is not None:
-                self._entry.register('w_dw', self.w_dw, lambda pc: pc._dw_weights())
-        return self.w_dw
-
     def _dw_eligible(self, d, gate=None, io=0):
         return (MFMA_BF16 and not MFMA_F32X3 and DW_BF16 and io == 3 and d.mode in (CONV_NORMAL, CONV_DECONV)
                 and gate is None and self.cin % 32 == 0 and self.cout % 8 == 0 and d.x_ld % 8 == 0 and d.x_coff % 8 == 0
                 and d.y_ld % 8 == 0 and d.y_coff % 8 == 0 and d.res_ld % 8 == 0)
-
-    def _patch_weights(self):
-        if self.w_patch is None:
-            lib = _lib.load()
-            w = self._keep
-            self.w_patch = torch.empty(lib.sgv3d_conv3x3_patch_bf16_weight_bytes(self.cout, self.cin), dtype=torch.uint8,
-                                       device=w.device)
-            with torch.cuda.device(w.device):
-                rc = lib.sgv3d_conv3x3_patch_bf16_pack_weight(w.data_ptr(), self.cout, self.cin, self.w_patch.data_ptr(), _st(w))
-            _lib.check(rc, "sgv3d_conv3x3_patch_bf16_pack_weight")
-            if self._entry is not None:
-                self._entry.register('w_patch', self.w_patch, lambda pc: pc._patch_weights())
-        return self.w_patch
 
     def out_hw(self, h, w):
         if self.transposed:
@@ -665,70 +596,65 @@ class PackedConv:
                     choice = self._rule(t, sk, d, gemm_m, gemm_n, gate)
             t, sk = choice
         d.tile, d.split_k = t, sk
-        # ALGORITHMIC flops: real channel counts, not the zero-padded ones the kernel multiplies
-        real_n = self.cout_real * (self.ks * self.ks if self.transposed else 1)
-        flops = 2.0 * gemm_m * real_n * (self.cin_real * self.kh * self.kw)
-        x3 = 10 < t < 20 or (MFMA_F32X3 is True and t < TILE_WINO)
-        name = ("conv_" if t in (TILE_WINO, TILE_WINO_RES, TILE_PATCH, TILE_WINO_HALF, TILE_F4RES) + WINO4_TILES + DW_TILES + PW_X3_TILES else
-                ("conv_igemm_bf16_" if MFMA_BF16 else "conv_igemm_f32x3_" if x3 else "conv_igemm_")) + TILE_NAMES[t]
-        plain = t not in (TILE_WINO, TILE_WINO_RES, TILE_PATCH, TILE_WINO_HALF, TILE_F4RES) + WINO4_TILES + DW_TILES + PW_X3_TILES
-        if plain and self.k_order == 0:
-            name += "_tapmajor"        # the <.., false> instantiation (cin % 32 != 0: stems), a different kernel symbol
-        elif plain and not MFMA_BF16 and not x3:
-            # the label names the INSTANTIATION launch_t (csrc/conv_igemm.hip) picks, so that a per-symbol rocprof / PMC
-            # summary can be attached to exactly this kernel (bench.py load_traffic): pointwise and five-per-CU forms
-            pw = (self.kh == 1 and self.kw == 1 and self.stride == 1 and self.pad == 0 and not self.transposed)
-            occ = t in OCC5_TILES
-            if pw and (occ or self.cin >= 128) and (occ or TILE_NAMES[t] in ("64x64", "64x128")):
-                name += "_pw"
-            if occ:
-                name += "_occ5"
-        # algorithmic bytes: input map (the channels this layer reads), weights, output (+ residual), each once
-        # (element sizes as the tensors are stored: bf16 activations in HBM count 2 bytes)
-        nbytes = (float(x.element_size()) * B * H * W * self.cin_real
-                  + (2.0 if MFMA_BF16 else 4.0) * self.cout_real * self.cin_real * self.kh * self.kw * (self.ks * self.ks if self.transposed else 1)
-                  + float(out.element_size()) * gemm_m * real_n
-                  + (float(residual.element_size()) * gemm_m * real_n if residual is not None else 0.0))
-        if PROFILE_DETAIL:
-            name += (f"|{B}x{H}x{W}x{self.cin}->{self.cout} k{self.kh if not self.transposed else -self.ks} "
-                     f"s{self.stride} d{self.dil} splitk{sk}" + (" mfirst" if 20 < t < 30 or t == 45 else "") + (" occ5" if t in OCC5_TILES else ""))
-        if io:
-            name = name.replace("conv_igemm_bf16_", "conv_igemm_bf16io_")
-        extra = None
-        if PROFILE is not None and not MFMA_BF16 and not x3:
-            b = lambda v: "true" if v else "false"
-            if plain:
-                wtm, wtn = (int(v) // 64 for v in TILE_NAMES[t].split("x"))
-                extra = {"symbol": f"conv_igemm_kernel<{wtm}, {wtn}, {b(self.k_order != 0)}, false, {b(name.endswith(('_pw', '_pw_occ5')))}, "
-                                   f"false, {b(t in OCC5_TILES)}>",
-                         "mfma_flops": 2.0 * gemm_m * self.cout * self.cin * self.kh * self.kw * (self.ks * self.ks if self.transposed else 1)}
-            elif t in PW_X3_TILES:
-                bm, bn = PW_X3_DIMS[t]
-                pw1 = self.kh == 1 and self.kw == 1 and self.stride == 1 and self.pad == 0
-                kk = (self.cin * self.kh * self.kw + 31) // 32 * 32
-                extra = {"symbol": f"conv_pw_x3_kernel<{bm // 16}, {bn // 32}, {2 if self.k_order == 0 else 0 if pw1 else 1}>",
-                         "mfma_flops": 2.0 * gemm_m * self.cout * kk, "bf16_mfma_flops": 6 * 2.0 * gemm_m * self.cout * kk}
-            elif t in WINO4_TILES:
-                # the grouped GEMM of the three-launch F(4x4) path: 36 positions x rows (tiles padded to the GEMM's m-tile)
-                dil = max(1, self.dil)
-                tiles = B * dil * dil * -(-(-(-oh // dil)) // 4) * -(-(-(-ow // dil)) // 4)
-                g = X3_TILE_ROWS[t] if t in WINO4_X3_TILES else 32 if t == TILE_WINO4_NARROW else 48 if t == TILE_WINO4_G48 else 64
-                rows = -(-tiles // g) * g
-                if t in WINO4_X3_TILES:
-                    # six bf16 partial products per f32 product: the kernel's roofline is the bf16 MFMA peak over these flops
-                    extra = {"symbol": f"gemm_x3_grouped_kernel<{g // 16}, {X3_TILE_COLS[t] // 32}>",
-                             "mfma_flops": 2.0 * 36 * rows * self.cin * self.cout, "bf16_mfma_flops": 6 * 2.0 * 36 * rows * self.cin * self.cout}
-                else:
-                    extra = {"symbol": {TILE_WINO4: "conv_igemm_kernel<1, 1, true, false, true, false, false>",
-                                        TILE_WINO4_WIDE: "conv_igemm_kernel<1, 2, true, false, true, false, false>",
-                                        TILE_WINO4_NARROW: "conv_igemm_kernel<1, 1, true, false, true, true, false>",
-                                        TILE_WINO4_OCC: "conv_igemm_kernel<1, 1, true, false, true, false, true>",
-                                        TILE_WINO4_G48: "gemm16_grouped_kernel<3>"}[t],
-                             "mfma_flops": 2.0 * 36 * rows * self.cin * self.cout}
+        name, flops, nbytes, extra = self._profile_record(TILES[t], sk, x, out, residual, gemm_m, io)
         with torch.cuda.device(x.device), prof(name, flops, nbytes, extra):
             rc = self._launch(lib, d, x, residual, gate, out, io)
         _lib.check(rc, "sgv3d_conv2d_forward")
         return out
+
+    def _profile_record(self, T, sk, x, out, residual, gemm_m, io):
+        """(label, algorithmic flops, algorithmic bytes, extra) of the launch with tile ``T`` for ``prof``.  The label names the
+        INSTANTIATION launch_t (csrc/conv_igemm.hip) picks and ``extra['symbol']`` is the MFMA kernel's exact symbol, so that a
+        per-symbol rocprof / PMC summary can be attached to exactly this kernel (bench.py load_traffic)."""
+        B, H, W, _ = (int(s) for s in x.shape)
+        ks2 = self.ks * self.ks if self.transposed else 1
+        # ALGORITHMIC flops (SURVEY 8d): real channel counts, not the zero-padded ones the kernel multiplies
+        real_n = self.cout_real * ks2
+        flops = 2.0 * gemm_m * real_n * (self.cin_real * self.kh * self.kw)
+        plain = T.family == "igemm"
+        x3 = plain and (T.x3 or (MFMA_F32X3 is True and not (T.mfirst or T.occ5)))
+        name = (("conv_igemm_bf16_" if MFMA_BF16 else "conv_igemm_f32x3_" if x3 else "conv_igemm_") if plain else "conv_") + T.label
+        pw1 = self.kh == 1 and self.kw == 1 and self.stride == 1 and self.pad == 0
+        if plain and self.k_order == 0:
+            name += "_tapmajor"        # the <.., false> instantiation (cin % 32 != 0: stems), a different kernel symbol
+        elif plain and not MFMA_BF16 and not x3:
+            # pointwise and five-per-CU forms
+            if pw1 and not self.transposed and (T.occ5 or self.cin >= 128) and (T.occ5 or T.bm == 64):
+                name += "_pw"
+            if T.occ5:
+                name += "_occ5"
+        # algorithmic bytes: input map (the channels this layer reads), weights, output (+ residual), each once
+        # (element sizes as the tensors are stored: bf16 activations in HBM count 2 bytes)
+        nbytes = (float(x.element_size()) * B * H * W * self.cin_real
+                  + (2.0 if MFMA_BF16 else 4.0) * self.cout_real * self.cin_real * self.kh * self.kw * ks2
+                  + float(out.element_size()) * gemm_m * real_n
+                  + (float(residual.element_size()) * gemm_m * real_n if residual is not None else 0.0))
+        if PROFILE_DETAIL:
+            name += (f"|{B}x{H}x{W}x{self.cin}->{self.cout} k{self.kh if not self.transposed else -self.ks} "
+                     f"s{self.stride} d{self.dil} splitk{sk}" + (" mfirst" if plain and T.mfirst else "") + (" occ5" if T.occ5 else ""))
+        if io:
+            name = name.replace("conv_igemm_bf16_", "conv_igemm_bf16io_")
+        extra = None
+        if PROFILE is not None and not MFMA_BF16 and not x3 and T.symbol:
+            b = lambda v: "true" if v else "false"
+            # ({pw}: as the label ENDS here -- with PROFILE_DETAIL the shape suffix follows and the flag reads false)
+            symbol = T.symbol.format(chunk=b(self.k_order != 0), pw=b(name.endswith(("_pw", "_pw_occ5"))),
+                                     kmode=2 if self.k_order == 0 else 0 if pw1 else 1)
+            if T.flops == "wino4":
+                # the grouped GEMM of the three-launch F(4x4) path: 36 positions x rows (tiles padded to the GEMM's m-tile)
+                oh, ow = self.out_hw(H, W)
+                dil = max(1, self.dil)
+                tiles = B * dil * dil * -(-(-(-oh // dil)) // 4) * -(-(-(-ow // dil)) // 4)
+                mfma = 2.0 * 36 * (-(-tiles // T.bm) * T.bm) * self.cin * self.cout
+            elif T.flops == "direct_k32":
+                mfma = 2.0 * gemm_m * self.cout * _up32(self.cin * self.kh * self.kw)
+            else:
+                mfma = 2.0 * gemm_m * self.cout * self.cin * self.kh * self.kw * ks2
+            extra = {"symbol": symbol, "mfma_flops": mfma}
+            if T.x3:
+                # six bf16 partial products per f32 product: the kernel's roofline is the bf16 MFMA peak over these flops
+                extra["bf16_mfma_flops"] = 6 * mfma
+        return name, flops, nbytes, extra
 
     def _rule(self, t, sk, d, gemm_m, gemm_n, gate=None):
         """Deterministic choice without measurement: Winograd for the layers it covers once the map has
@@ -758,102 +684,85 @@ class PackedConv:
                 and (d.res_ld % 8 == 0))
 
     def _launch(self, lib, d, x, residual, gate, out, io=0):
+        """Launch the kernel that host tile ``d.tile`` names (conv_tiles.TILES): its family's launcher, which checks that the kernel
+        covers this layer and launch and hands the entry point a copy of ``d`` in the ABI's terms (``_abi``)."""
+        T = TILES[d.tile]
         ws, nws = None, 0
-        if d.split_k > 1 and d.tile not in DW_TILES:
+        if d.split_k > 1 and T.family != "dw_bf16":
             nws = lib.sgv3d_conv2d_workspace_bytes(ctypes.byref(d))
             ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
-        if d.tile == TILE_PATCH:
-            if not self._patch_eligible(d, gate):
-                raise _lib.SGV3DError("the bf16 patch kernel covers 3x3 / stride 1 / pad 1 layers with cin % 32 == 0 in bf16 mode")
-            return lib.sgv3d_conv3x3_patch_bf16_forward(d.batch, d.in_h, d.in_w, self.cin, self.cout, d.x_ld, d.x_coff, d.y_ld,
-                                                        d.y_coff, d.res_ld, d.relu, x.data_ptr(), self._patch_weights().data_ptr(),
-                                                        _lib.ptr(self.scale), _lib.ptr(self.shift), _lib.ptr(residual),
-                                                        out.data_ptr(), int(io), int(d.split_k), _lib.ptr(ws), nws, _st(x))
-        if d.tile in DW_TILES:
-            if not self._dw_eligible(d, gate, io) or (d.split_k > 1 and d.mode != CONV_NORMAL):
-                raise _lib.SGV3DError("the bf16 direct-weight kernel covers layers with cin % 32 == 0, cout % 8 == 0 and bf16 tensors in "
-                                      "and out (NHWC), no gate; split-K in NORMAL mode only")
-            if d.split_k > 1:
-                nws = lib.sgv3d_conv_dw_bf16_workspace_bytes(ctypes.byref(d))
-                ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
-                return lib.sgv3d_conv_dw_bf16_forward_splitk(ctypes.byref(d), x.data_ptr(), self._dw_weights().data_ptr(),
-                                                             _lib.ptr(self.scale), _lib.ptr(self.shift), _lib.ptr(residual), out.data_ptr(),
-                                                             ws.data_ptr(), nws, _st(x))
-            return lib.sgv3d_conv_dw_bf16_forward(ctypes.byref(d), x.data_ptr(), self._dw_weights().data_ptr(), _lib.ptr(self.scale),
-                                                  _lib.ptr(self.shift), _lib.ptr(residual), out.data_ptr(), _st(x))
-        if d.tile == TILE_F4RES:
-            if not self.f4res_ok(d, gate, io) or d.split_k > 1 or x.dtype != torch.float32:
-                raise _lib.SGV3DError("the resident F(4x4) kernel covers f32 3x3 / stride 1 / pad 1 layers with 64 input channels "
-                                      "(cout % 64 == 0) or 64 output channels (cin % 64 == 0), NHWC output, no gate, no split-K")
-            return lib.sgv3d_conv3x3_f4res_forward(ctypes.byref(d), x.data_ptr(), self._f4res_weights().data_ptr(), _lib.ptr(self.scale),
-                                                   _lib.ptr(self.shift), _lib.ptr(residual), out.data_ptr(), _st(x))
-        if d.tile in PW_X3_TILES:
-            if not self.pw_x3_ok(d, gate, io) or x.dtype != torch.float32:
-                raise _lib.SGV3DError("the implicit-GEMM f32x3 kernel covers f32 layers with at most 32 taps, cin % 32 == 0 (>= 64), cout % 4 == 0, "
-                                      "NHWC output, no gate")
-            u = self._pw_x3_weights()
-            host_tile, cp = d.tile, d.cout_pad
-            # SGV3D_TILE_X3 | variant [| SGV3D_TILE_MFIRST]: 6x / 7x: variant = t % 10; 8x / 9x: 8 + t % 10 (256-channel tiles)
-            d.tile = 64 | ((host_tile % 10) + (8 if host_tile >= 80 else 0)) | (16 if host_tile // 10 in (7, 9) else 0)
-            d.cout_pad = self.pw_x3_cout_pad
-            try:
-                return lib.sgv3d_conv2d_x3_forward(ctypes.byref(d), x.data_ptr(), u.data_ptr(), _lib.ptr(self.scale), _lib.ptr(self.shift),
-                                                   _lib.ptr(residual), out.data_ptr(), _lib.ptr(ws), nws, _st(x))
-            finally:
-                d.tile, d.cout_pad = host_tile, cp
-        if d.tile in WINO4_TILES:
-            if not self.wino4_ok(d, gate) or d.split_k > 1:
-                raise _lib.SGV3DError("F(4x4) Winograd covers f32 3x3 / stride 1 / pad 1 layers with cin % 32 == 0, cout % 4 == 0, "
-                                      "NHWC output, no gate, no split-K")
-            host_tile, kp, cp = d.tile, d.k_pad, d.cout_pad
-            if host_tile in WINO4_X3_TILES:
-                u = self._wino4_x3_weights()
-                d.tile = 64 | (host_tile - 50)                     # SGV3D_TILE_X3 | variant
-                d.k_pad, d.cout_pad = self.cin, self.wino4_x3_cout_pad
-            else:
-                u = self._wino4_weights()
-                d.tile = {TILE_WINO4: 4, TILE_WINO4_WIDE: 3, TILE_WINO4_NARROW: 9, TILE_WINO4_OCC: 4 | 32,
-                          TILE_WINO4_G48: 10}[host_tile]      # SGV3D_TILE_64x64 / 64x128 / 32x128 / 64x64 | OCC5 / 48x64
-                d.k_pad, d.cout_pad = self.wino4_geom
-            try:
-                nws4 = lib.sgv3d_conv2d_winograd4_workspace_bytes(ctypes.byref(d))
-                ws4 = torch.empty(nws4, dtype=torch.uint8, device=x.device)
-                return lib.sgv3d_conv2d_winograd4_forward(ctypes.byref(d), x.data_ptr(), u.data_ptr(), _lib.ptr(self.scale),
-                                                          _lib.ptr(self.shift), _lib.ptr(residual), out.data_ptr(), ws4.data_ptr(),
-                                                          nws4, _st(x))
-            finally:
-                d.tile, d.k_pad, d.cout_pad = host_tile, kp, cp
-        if d.tile in (TILE_WINO, TILE_WINO_RES, TILE_WINO_HALF):
-            if not self.wino_ok:
-                raise _lib.SGV3DError("this layer has no Winograd weights (needs 3x3 / stride 1 / pad 1 / cin % 8 == 0)")
-            return lib.sgv3d_conv2d_winograd_forward(ctypes.byref(d), x.data_ptr(), self.w_wino.data_ptr(),
-                                                     _lib.ptr(self.scale), _lib.ptr(self.shift), _lib.ptr(residual),
-                                                     _lib.ptr(gate), out.data_ptr(), _lib.ptr(ws), nws, _st(x))
-        x3 = 10 < d.tile < 20 or (MFMA_F32X3 is True)
-        host_tile = d.tile
-        if host_tile in OCC5_TILES:
-            if MFMA_BF16 or x3 or io or self.k_order != 1:
-                raise _lib.SGV3DError("the five-per-CU 64x64 tile is f32 only and needs channel-chunk-major weights (cin % 32 == 0)")
-            d.tile = 4 | 32 | (16 if host_tile == 45 else 0)      # SGV3D_TILE_64x64 | SGV3D_TILE_OCC5 [| SGV3D_TILE_MFIRST]
-        elif host_tile > 20:
-            d.tile = (host_tile - 20) | 16          # SGV3D_TILE_MFIRST
-        elif host_tile > 10:
-            d.tile = host_tile - 10
+        tail = (_lib.ptr(self.scale), _lib.ptr(self.shift), _lib.ptr(residual))
+        return getattr(self, "_launch_" + T.entry)(lib, T, d, x, tail, gate, out, io, ws, nws)
+
+    @staticmethod
+    def _abi(d, T, k_pad=None, cout_pad=None):
+        """``byref`` of a copy of the descriptor with ``tile`` as the entry point reads it (and the geometry of the weight form the
+        kernel reads, where that is not the implicit-GEMM one).  ``d`` itself keeps the host id."""
+        a = ConvDesc.from_buffer_copy(d)
+        if T.abi is not None:
+            a.tile = T.abi
+        if k_pad is not None:
+            a.k_pad, a.cout_pad = k_pad, cout_pad
+        return ctypes.byref(a)
+
+    def _launch_conv2d(self, lib, T, d, x, tail, gate, out, io, ws, nws):
+        x3 = T.x3 or (MFMA_F32X3 is True)
+        if T.occ5 and (MFMA_BF16 or x3 or io or self.k_order != 1):
+            raise _lib.SGV3DError("the five-per-CU 64x64 tile is f32 only and needs channel-chunk-major weights (cin % 32 == 0)")
         if io:
-            try:
-                return lib.sgv3d_conv2d_forward_bf16io(ctypes.byref(d), x.data_ptr(), self._bf16_weights().data_ptr(), _lib.ptr(self.scale),
-                                                       _lib.ptr(self.shift), _lib.ptr(residual), _lib.ptr(gate), out.data_ptr(),
-                                                       _lib.ptr(ws), nws, _st(x), int(io))
-            finally:
-                d.tile = host_tile
+            return lib.sgv3d_conv2d_forward_bf16io(self._abi(d, T), x.data_ptr(), self._bf16_weights().data_ptr(), *tail, _lib.ptr(gate),
+                                                   out.data_ptr(), _lib.ptr(ws), nws, _st(x), int(io))
         fwd = (lib.sgv3d_conv2d_forward_bf16 if MFMA_BF16 else
                lib.sgv3d_conv2d_forward_f32x3 if x3 else lib.sgv3d_conv2d_forward)
-        try:
-            return fwd(ctypes.byref(d), x.data_ptr(), self.w.data_ptr(), _lib.ptr(self.scale),
-                       _lib.ptr(self.shift), _lib.ptr(residual), _lib.ptr(gate), out.data_ptr(),
-                       _lib.ptr(ws), nws, _st(x))
-        finally:
-            d.tile = host_tile
+        return fwd(self._abi(d, T), x.data_ptr(), self.w.data_ptr(), *tail, _lib.ptr(gate), out.data_ptr(), _lib.ptr(ws), nws, _st(x))
+
+    def _launch_winograd(self, lib, T, d, x, tail, gate, out, io, ws, nws):
+        if not self.wino_ok:
+            raise _lib.SGV3DError("this layer has no Winograd weights (needs 3x3 / stride 1 / pad 1 / cin % 8 == 0)")
+        return lib.sgv3d_conv2d_winograd_forward(self._abi(d, T), x.data_ptr(), self.w_wino.data_ptr(), *tail, _lib.ptr(gate),
+                                                 out.data_ptr(), _lib.ptr(ws), nws, _st(x))
+
+    def _launch_winograd4(self, lib, T, d, x, tail, gate, out, io, ws, nws):
+        if not self.wino4_ok(d, gate) or d.split_k > 1:
+            raise _lib.SGV3DError("F(4x4) Winograd covers f32 3x3 / stride 1 / pad 1 layers with cin % 32 == 0, cout % 4 == 0, "
+                                  "NHWC output, no gate, no split-K")
+        u = self._form(T.form)
+        a = self._abi(d, T, self.cin, self.wino4_x3_cout_pad) if T.x3 else self._abi(d, T, *self.wino4_geom)
+        nws4 = lib.sgv3d_conv2d_winograd4_workspace_bytes(a)
+        ws4 = torch.empty(nws4, dtype=torch.uint8, device=x.device)
+        return lib.sgv3d_conv2d_winograd4_forward(a, x.data_ptr(), u.data_ptr(), *tail, out.data_ptr(), ws4.data_ptr(), nws4, _st(x))
+
+    def _launch_f4res(self, lib, T, d, x, tail, gate, out, io, ws, nws):
+        if not self.f4res_ok(d, gate, io) or d.split_k > 1 or x.dtype != torch.float32:
+            raise _lib.SGV3DError("the resident F(4x4) kernel covers f32 3x3 / stride 1 / pad 1 layers with 64 input channels "
+                                  "(cout % 64 == 0) or 64 output channels (cin % 64 == 0), NHWC output, no gate, no split-K")
+        return lib.sgv3d_conv3x3_f4res_forward(self._abi(d, T), x.data_ptr(), self._form(T.form).data_ptr(), *tail, out.data_ptr(), _st(x))
+
+    def _launch_x3(self, lib, T, d, x, tail, gate, out, io, ws, nws):
+        if not self.pw_x3_ok(d, gate, io) or x.dtype != torch.float32:
+            raise _lib.SGV3DError("the implicit-GEMM f32x3 kernel covers f32 layers with at most 32 taps, cin % 32 == 0 (>= 64), cout % 4 == 0, "
+                                  "NHWC output, no gate")
+        u = self._form(T.form)
+        return lib.sgv3d_conv2d_x3_forward(self._abi(d, T, d.k_pad, self.pw_x3_cout_pad), x.data_ptr(), u.data_ptr(), *tail, out.data_ptr(),
+                                           _lib.ptr(ws), nws, _st(x))
+
+    def _launch_patch_bf16(self, lib, T, d, x, tail, gate, out, io, ws, nws):
+        if not self._patch_eligible(d, gate):
+            raise _lib.SGV3DError("the bf16 patch kernel covers 3x3 / stride 1 / pad 1 layers with cin % 32 == 0 in bf16 mode")
+        return lib.sgv3d_conv3x3_patch_bf16_forward(d.batch, d.in_h, d.in_w, self.cin, self.cout, d.x_ld, d.x_coff, d.y_ld,
+                                                    d.y_coff, d.res_ld, d.relu, x.data_ptr(), self._patch_weights().data_ptr(),
+                                                    *tail, out.data_ptr(), int(io), int(d.split_k), _lib.ptr(ws), nws, _st(x))
+
+    def _launch_dw_bf16(self, lib, T, d, x, tail, gate, out, io, ws, nws):
+        if not self._dw_eligible(d, gate, io) or (d.split_k > 1 and d.mode != CONV_NORMAL):
+            raise _lib.SGV3DError("the bf16 direct-weight kernel covers layers with cin % 32 == 0, cout % 8 == 0 and bf16 tensors in "
+                                  "and out (NHWC), no gate; split-K in NORMAL mode only")
+        if d.split_k > 1:
+            nws = lib.sgv3d_conv_dw_bf16_workspace_bytes(ctypes.byref(d))
+            ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
+            return lib.sgv3d_conv_dw_bf16_forward_splitk(self._abi(d, T), x.data_ptr(), self._dw_weights().data_ptr(), *tail,
+                                                         out.data_ptr(), ws.data_ptr(), nws, _st(x))
+        return lib.sgv3d_conv_dw_bf16_forward(self._abi(d, T), x.data_ptr(), self._dw_weights().data_ptr(), *tail, out.data_ptr(), _st(x))
 
     def _time_under_load(self, lib, d, x, residual, gate, out, rounds=None, io=0):
         """Time for TUNE_STREAMS concurrent copies of the launch, ``rounds`` back to back on every stream (all copies
@@ -884,15 +793,14 @@ class PackedConv:
         """The (tile, (split-K, ...)) pairs this layer may run with on this input / output layout under the module's current
         switches (WINOGRAD, WINO4, WINO_HALF, PATCH_BF16, DW_*, SPLIT_K, MFIRST, MFMA_*): what the first-call measurement times,
         and what a tune-DB entry is checked against before it is trusted (``_db_choice``)."""
-        tiles = (1, 2, 3, 4)
-        if MFIRST and d.mode in (CONV_NORMAL, CONV_NCHW_OUT) and gemm_n > 64:
-            tiles += tuple(t + 20 for t in (1, 2, 3, 4) if gemm_n > (128 if t in (1, 3) else 64))   # more than one channel tile
+        sel = conv_tiles.select
+        # an m-tile-first walk needs more than one channel tile
+        mfirst = lambda t: MFIRST and d.mode in (CONV_NORMAL, CONV_NCHW_OUT) and gemm_n > TILES[t].bn
+        tiles = sel("igemm") + tuple(t for t in sel("igemm", mfirst=True) if mfirst(t))
         if OCC5 and self.k_order == 1 and not MFMA_BF16 and not MFMA_F32X3 and io == 0:
-            tiles += (44,)
-            if MFIRST and d.mode in (CONV_NORMAL, CONV_NCHW_OUT) and gemm_n > 64:
-                tiles += (45,)
+            tiles += sel("igemm", occ5=True) + tuple(t for t in sel("igemm", occ5=True, mfirst=True) if mfirst(t))
         if MFMA_F32X3 == "auto" and not MFMA_BF16:
-            tiles += (11, 12, 13, 14)
+            tiles += sel("igemm", x3=True)
         if self.wino_ok and WINOGRAD and not MFMA_BF16:
             tiles += (TILE_WINO,)
             if WINO_HALF:
@@ -912,57 +820,46 @@ class PackedConv:
             for t in PW_X3_TILES:
                 bm, bn = PW_X3_DIMS[t]
                 wgs = -(-gemm_m // bm) * -(-gemm_n // bn)
-                mfirst = t // 10 in (7, 9)
                 if bn == 256 and gemm_n < 256:
                     continue
-                if (wgs >= 96 or (SPLIT_K and nkt >= 16)) and (bn >= 128 or gemm_n <= 64 or wgs < 1024) and (not mfirst or (MFIRST and gemm_n > bn)):
+                if (wgs >= 96 or (SPLIT_K and nkt >= 16)) and (bn >= 128 or gemm_n <= 64 or wgs < 1024) and (not TILES[t].mfirst or (MFIRST and gemm_n > bn)):
                     tiles += (t,)
         if self._patch_eligible(d, gate):
             tiles += (TILE_PATCH,)
         if self._dw_eligible(d, gate, io):
+            dw = lambda bm, bn, deep=False: (conv_tiles.by_shape("dw_bf16", bm, bn, deep),)
             deep = self.kh * self.kw * self.cin >= 512              # enough k for the 128-pixel wave tiles to pay
-            tiles += ((31,) + ((34,) if deep else ()) if gemm_n > 128 else (32,) + ((35,) if deep else ()) if gemm_n > 64 else (32, 33))
+            tiles += (dw(64, 256) + (dw(128, 256) if deep else ()) if gemm_n > 128 else
+                      dw(128, 128) + (dw(256, 128) if deep else ()) if gemm_n > 64 else dw(128, 128) + dw(256, 64))
             if DW_DEEP and self.kh * self.kw * self.cin >= 256:     # few workgroups per CU: the two-chunks-ahead form of the 64-pixel tiles
                 if gemm_n > 128 and -(-gemm_m // 64) * -(-gemm_n // 256) <= DW_DEEP_MAX_WGS:
-                    tiles += (36,)
+                    tiles += dw(64, 256, True)
                     if DW_NARROW and -(-gemm_m // 64) * -(-gemm_n // 256) <= 384:
-                        tiles += (38, 39)
+                        tiles += dw(64, 128) + dw(64, 128, True)
                 elif 64 < gemm_n <= 128 and -(-gemm_m // 128) * -(-gemm_n // 128) <= DW_DEEP_MAX_WGS:
-                    tiles += (37,)
+                    tiles += dw(128, 128, True)
         if fixed_tile:
             tiles = (fixed_tile,)
-        dims = {1: (128, 128), 2: (128, 64), 3: (64, 128), 4: (64, 64), 5: (256, 64), 6: (256, 64),
-                11: (128, 128), 12: (128, 64), 13: (64, 128), 14: (64, 64),
-                21: (128, 128), 22: (128, 64), 23: (64, 128), 24: (64, 64), 44: (64, 64), 45: (64, 64)}
-        dims.update(PW_X3_DIMS)
         cands = []
         for t in tiles:
-            bm, bn = dims.get(t, (512, 64))
-            wgs = -(-gemm_m // bm) * -(-gemm_n // bn)
+            T = TILES[t]
+            wgs = -(-gemm_m // T.bm) * -(-gemm_n // T.bn)
             nk = nkt
-            if t in (TILE_WINO, TILE_WINO_HALF):
-                nk = self.cin // 4      # k-steps of 8 channels; nk // s >= 8 keeps >= 4 steps per split
-                wgs = d.batch * -(-d.out_h // 16) * -(-d.out_w // 16) * -(-gemm_n // (64 if t == TILE_WINO else 32))
-            if t == TILE_PATCH:
-                nk = self.cin // 32     # stages of 32 input channels; >= 2 per split
-                wgs = d.batch * -(-d.out_h // 16) * -(-d.out_w // 32) * -(-gemm_n // 64)
-            if t in DW_TILES:
+            if T.spatial:
+                th, tw, kc = T.spatial
+                nk = self.cin // kc     # F(2x2): k-steps of 8 channels, nk // s >= 8 keeps >= 4 steps per split; patch: stages of 32, >= 2 per split
+                wgs = d.batch * -(-d.out_h // th) * -(-d.out_w // tw) * -(-gemm_n // T.bn)
+            if T.family == "dw_bf16":
                 nk = -(-(self.kh * self.kw * (self.cin // 32)) // 2)      # chunks of 64 k; >= 4 per split
-                bm, bn = {31: (64, 256), 32: (128, 128), 33: (256, 64), 34: (128, 256), 35: (256, 128), 36: (64, 256), 37: (128, 128), 38: (64, 128), 39: (64, 128)}[t]
-                wgs = -(-gemm_m // bm) * -(-gemm_n // bn)
-            if t in (TILE_WINO_RES, TILE_F4RES) or t in WINO4_TILES or t in DW_DEEP_TILES or (t in DW_TILES and (d.mode != CONV_NORMAL or not DW_SPLIT_K)):
+            if T.split is None or (T.family == "dw_bf16" and (d.mode != CONV_NORMAL or not DW_SPLIT_K)):
                 splits = (1,)
-            elif t in DW_TILES:
-                splits = (fixed_split,) if fixed_split else \
-                    [1] + [s for s in (2, 3, 4, 6, 8) if SPLIT_K and nk // s >= 4 and wgs < 384 and wgs * s <= 1024]
-            elif t == TILE_PATCH and not fixed_split and SPLIT_K:
-                splits = [1] + [s for s in (2, 3, 4, 6, 8) if nk // s >= 2 and wgs * s <= 1024]
             elif fixed_split:
                 splits = (fixed_split,)
             elif not SPLIT_K:
                 splits = (1,)
             else:
-                splits = [1] + [s for s in (2, 3, 4, 6, 8) if nk // s >= 4 and wgs < 2048 and wgs * s <= 6144]
+                pol = conv_tiles.SPLIT_POLICY[T.split]
+                splits = [1] + [s for s in conv_tiles.SPLITS if nk // s >= pol["min_k"] and wgs < pol["max_wgs"] and wgs * s <= pol["max_total"]]
             cands.append((t, tuple(splits)))
         return cands
 
@@ -971,12 +868,12 @@ class PackedConv:
         (the smallest waste always), 160 columns only where they cover cout with fewer idle columns than 128 do."""
         dil = max(1, int(d.dil))
         tiles = d.batch * dil * dil * -(-(-(-d.out_h // dil)) // 4) * -(-(-(-d.out_w // dil)) // 4)
-        waste = {r: (-(-tiles // r) * r - tiles) / tiles for r in (48, 64, 96, 112, 128)}
+        waste = {r: (-(-tiles // r) * r - tiles) / tiles for r in sorted(set(X3_TILE_ROWS.values()))}
         best = min(waste.values())
-        ms = [i for i, r in enumerate((48, 64, 96, 112, 128)) if waste[r] <= max(best, 0.10) and (r <= 64 or tiles >= r)]
+        ms = [r for r in waste if waste[r] <= max(best, 0.10) and (r <= 64 or tiles >= r)]
         idle = lambda c: -(-self.cout // c) * c - self.cout
-        ws = [0] + ([5] if idle(160) < idle(128) else [])
-        return tuple(50 + w + m for w in ws for m in ms)
+        cols = [128] + ([160] if idle(160) < idle(128) else [])
+        return tuple(conv_tiles.by_shape("wino4_x3", r, c) for c in cols for r in ms)
 
     def _db_choice(self, sig, d, x, gate, gemm_m, gemm_n, nkt, fixed_tile, fixed_split, io=0):
         """The tune-DB entry of ``sig`` if it is one of the candidates this layer would be measured with right now, else None

@@ -9,6 +9,7 @@ import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from sgv3d_amd import hip_ops
 from sgv3d_amd.hip_ops import PackedConv, TILE_WINO, TILE_WINO_RES, TILE_WINO_HALF
+from sgv3d_amd.conv_tiles import TILES, select
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 300
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
@@ -51,9 +52,9 @@ for it in range(N):
         ref = ref * gate.double()[:, None, None, :]
     conv = PackedConv(w.cuda(), stride=stride, pad=pad, dil=dil, scale=None if sc is None else sc.cuda(),
                       shift=None if sh is None else sh.cuda(), relu=use_relu)
-    cands = [(t, s) for t in (1, 2, 3, 4, 21, 22, 23, 24) for s in (1, 2, 3)]      # 21..24: the same tiles walked m-tile first
+    cands = [(t, s) for t in select("igemm") + select("igemm", mfirst=True) for s in (1, 2, 3)]      # (the same tiles walked m-tile first)
     if conv.k_order == 1 and MODE not in ("bf16", "f32x3"):
-        cands += [(t, s) for t in (44, 45) for s in (1, 2, 3)]      # the 64x64 tile at five workgroups per CU (44; 45: m-tile first)
+        cands += [(t, s) for t in hip_ops.OCC5_TILES for s in (1, 2, 3)]      # the 64x64 tile at five workgroups per CU
     if conv.w_wino is not None and MODE != "bf16":
         cands += [(TILE_WINO, 1), (TILE_WINO, 2), (TILE_WINO, 3), (TILE_WINO_HALF, 1), (TILE_WINO_HALF, 2), (TILE_WINO_HALF, 3)]
         if cin <= 96:
@@ -61,12 +62,13 @@ for it in range(N):
     # round 6: the f32x3 kernels -- implicit GEMM (tiles 60-92 x split-K, csrc/conv_pw_x3.hip) and the F(4x4) position GEMM (50-59)
     if MODE == "f32" and not use_gate and cout % 4 == 0:
         if conv.pw_x3_ok():
-            cands += [(t, s) for t in hip_ops.PW_X3_TILES for s in (1, 2, 3) if t < 80 or cout >= 256]
+            cands += [(t, s) for t in hip_ops.PW_X3_TILES for s in (1, 2, 3) if TILES[t].bn < 256 or cout >= 256]
         if conv.wino4_ok():
             cands += [(t, 1) for t in hip_ops.WINO4_X3_TILES]
     scale_ref = max(1.0, ref.abs().max().item())
     for t, s in cands:
-        nk = (cin * k * k + 31) // 32 if t in hip_ops.PW_X3_TILES else conv.k_pad // 32 if (t < TILE_WINO or t > 20) else cin // 8      # (Winograd variants: k-steps of 8 channels)
+        fam = TILES[t].family
+        nk = (cin * k * k + 31) // 32 if fam == "pw_x3" else cin // 8 if fam == "wino" else conv.k_pad // 32      # (F(2x2) Winograd: k-steps of 8 channels)
         if s > nk:
             continue
         out = torch.full((B, OH, OW, cout + y_extra), -7.0, device="cuda")

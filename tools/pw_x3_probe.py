@@ -56,8 +56,8 @@ def main():
             torch.cuda.synchronize()
             err = float((out.double() - want).abs().max()) / scale
             row.append((graph_us(fn, reps=10), t, sk, err))
-        f32 = min(r for r in row if r[1] < 60)
-        x3 = sorted(r for r in row if r[1] >= 60)
+        f32 = min(r for r in row if r[1] not in hip_ops.PW_X3_TILES)
+        x3 = sorted(r for r in row if r[1] in hip_ops.PW_X3_TILES)
         print(f"{name:24s} f32 best {f32[0]:6.1f} us (tile {f32[1]} sk{f32[2]}, e={f32[3]:.1e}) | x3: " +
               " ".join(f"{t}/sk{k}:{us:.1f}" for us, t, k, _ in x3[:5]) + f" | worst x3 err {max(r[3] for r in x3):.1e}", flush=True)
 
