@@ -730,6 +730,42 @@ int sgv3d_centerpoint_merge_tasks(int batch, int num_tasks, int max_num, const f
                                   const int32_t *labels, const unsigned char *keep, const int32_t *classes_per_task /*host*/,
                                   float *out_boxes, float *out_scores, int32_t *out_labels, int32_t *counts, void *stream);
 
+/* nms_type='rotate' of mmdet3d 0.18.1 CenterHead.get_bboxes: greedy rotated-IoU BEV NMS in place of circle NMS.  PARITY
+ * UNPINNED (mmdet3d is not available): the definition is DESIGN.md "Box decode: nms_type='rotate'".
+ *
+ * The geometry on the CPU, the very functions the kernel runs: iou[k] = IoU of the BEV rectangles a5[k] and b5[k],
+ * (x, y, d0, d1, yaw) each, a corner offset (ox, oy) mapped to (ox cos + oy sin, -ox sin + oy cos), float32 with a5[k]'s
+ * centre as the origin; 0 when either box is degenerate (non-finite centre / yaw, extent not finite and positive). */
+int sgv3d_rotated_bev_iou_host(int n, const float *a5 /*host*/, const float *b5 /*host*/, float *iou /*host*/);
+
+/* The NMS stage alone, one launch over the stacked candidates of sgv3d_centerpoint_decode_tasks:
+ *   boxes f32 [num_tasks, batch, max_num, 9], scores f32 / valid u8 [num_tasks, batch, max_num] in candidate order.
+ *   A candidate takes part when valid and (score_threshold <= 0 or score >= score_threshold); only the first pre_max_size of
+ *   those; j is suppressed by an earlier kept i when IoU(i, j) > nms_thr[task] (host float[num_tasks] >= 0, <= 16 tasks); the first
+ *   post_max_size survivors remain (a cap <= 0: none); of these keep u8 [num_tasks, batch, max_num] marks the ones whose
+ *   centre (x, y, z) lies in limit_range (host float[6], inclusive; NULL: all).
+ *   max_num <= 1024; above 512 the suppression bit matrix lives in the workspace (8-byte aligned). */
+size_t sgv3d_rotate_nms_workspace_bytes(int batch, int num_tasks, int max_num);
+int sgv3d_rotate_nms(int batch, int num_tasks, int max_num, const float *boxes, const float *scores,
+                     const unsigned char *valid, float score_threshold, const float *nms_thr /*host*/, int pre_max_size,
+                     int post_max_size, const float *limit_range /*host*/, void *workspace, size_t workspace_bytes,
+                     unsigned char *keep, void *stream);
+
+/* sgv3d_centerpoint_decode_tasks with the rotated NMS: the same candidate stage, then sgv3d_rotate_nms (three launches).
+ * Outputs as there, so that sgv3d_centerpoint_merge_tasks follows unchanged.  score_threshold / post_center_range are the
+ * coder's (valid); nms_score_threshold .. limit_range are the NMS stage's. */
+size_t sgv3d_centerpoint_decode_tasks_rotate_workspace_bytes(int batch, int num_tasks, int max_class, int max_num);
+int sgv3d_centerpoint_decode_tasks_rotate(int batch, int num_tasks, const int32_t *classes_per_task /*host*/, int h, int w,
+                                          int max_num, const void *const *heatmap, const void *const *reg,
+                                          const void *const *height, const void *const *dim, const void *const *rot,
+                                          const void *const *vel, long long batch_stride, float out_size_factor, float voxel_x,
+                                          float voxel_y, float pc_x, float pc_y, float score_threshold,
+                                          const float *post_center_range /*host*/, int norm_bbox, float nms_score_threshold,
+                                          const float *nms_thr /*host*/, int pre_max_size, int post_max_size,
+                                          const float *limit_range /*host*/, void *workspace, size_t workspace_bytes,
+                                          float *boxes, float *scores, int32_t *labels, unsigned char *valid,
+                                          unsigned char *keep, void *stream);
+
 /* ================================================================================================
  * Training-side head functions  
  * ================================================================================================ */

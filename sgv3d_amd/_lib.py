@@ -136,6 +136,15 @@ _PROTOS = {
                                        [ctypes.POINTER(ctypes.c_float), c_int, ctypes.POINTER(ctypes.c_float), c_int, c_void_p,
                                         c_size_t] + [c_void_p] * 6),
     "sgv3d_centerpoint_merge_tasks": (c_int, [c_int] * 3 + [c_void_p] * 4 + [ctypes.POINTER(ctypes.c_int32)] + [c_void_p] * 5),
+    "sgv3d_rotated_bev_iou_host": (c_int, [c_int] + [ctypes.POINTER(ctypes.c_float)] * 3),
+    "sgv3d_rotate_nms_workspace_bytes": (c_size_t, [c_int] * 3),
+    "sgv3d_rotate_nms": (c_int, [c_int] * 3 + [c_void_p] * 3 + [ctypes.c_float, ctypes.POINTER(ctypes.c_float), c_int, c_int,
+                                                                ctypes.POINTER(ctypes.c_float), c_void_p, c_size_t, c_void_p, c_void_p]),
+    "sgv3d_centerpoint_decode_tasks_rotate_workspace_bytes": (c_size_t, [c_int] * 4),
+    "sgv3d_centerpoint_decode_tasks_rotate": (c_int, [c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_int, c_int] +
+                                              [ctypes.POINTER(c_void_p)] * 6 + [c_ll] + [ctypes.c_float] * 6 +
+                                              [ctypes.POINTER(ctypes.c_float), c_int, ctypes.c_float, ctypes.POINTER(ctypes.c_float),
+                                               c_int, c_int, ctypes.POINTER(ctypes.c_float), c_void_p, c_size_t] + [c_void_p] * 6),
     "sgv3d_centerhead_targets": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(ctypes.c_int32)] +
                                  [c_int] * 3 + [ctypes.c_float] * 5 + [ctypes.c_double, c_int, c_int] + [c_void_p] * 5),
     "sgv3d_conv2d_backward_weight_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvDesc), c_int]),

@@ -469,19 +469,20 @@ extern "C" size_t sgv3d_centerpoint_decode_tasks_workspace_bytes(int batch, int 
     return (sizeof(float) + sizeof(int)) * (size_t)num_tasks * batch * max_class * max_num + 256;
 }
 
-extern "C" int sgv3d_centerpoint_decode_tasks(int batch, int num_tasks, const int32_t *classes_per_task, int h, int w, int max_num,
-                                              const void *const *heatmap, const void *const *reg, const void *const *height,
-                                              const void *const *dim, const void *const *rot, const void *const *vel,
-                                              long long batch_stride, float out_size_factor, float voxel_x, float voxel_y,
-                                              float pc_x, float pc_y, float score_threshold, const float *post_center_range,
-                                              int norm_bbox, const float *nms_thresh, int post_max_size, void *workspace,
-                                              size_t workspace_bytes, float *boxes, float *scores, int32_t *labels,
-                                              unsigned char *valid, unsigned char *keep, void *stream) {
+// The candidate stage both NMS types share: argument checks (reported under the entry's name `who`), then top-k per class
+// and merge + box assembly (two launches).  `ts` is left filled with the maps and class counts; the NMS parameters are
+// the caller's (`nms_param`, its per-task host array, is only tested for null here, in the place it always was).
+static int decode_candidates(const char *who, int batch, int num_tasks, const int32_t *classes_per_task, int h, int w, int max_num,
+                             const void *const *heatmap, const void *const *reg, const void *const *height,
+                             const void *const *dim, const void *const *rot, const void *const *vel, long long batch_stride,
+                             float out_size_factor, float voxel_x, float voxel_y, float pc_x, float pc_y, float score_threshold,
+                             const float *post_center_range, int norm_bbox, const float *nms_param, void *workspace,
+                             size_t workspace_bytes, float *boxes, float *scores, int32_t *labels, unsigned char *valid,
+                             unsigned char *keep, hipStream_t st, DecodeTasks &ts) {
     SGV3D_REQUIRE(batch > 0 && num_tasks > 0 && num_tasks <= kMaxTasks && h > 0 && w > 0 && max_num > 0,
-                  "centerpoint_decode: non-positive size (or more than %d tasks)", kMaxTasks);
-    SGV3D_REQUIRE(classes_per_task && heatmap && reg && height && dim && rot && nms_thresh && boxes && scores && labels && valid &&
-                  keep && workspace, "centerpoint_decode: null pointer");
-    DecodeTasks ts;
+                  "%s: non-positive size (or more than %d tasks)", who, kMaxTasks);
+    SGV3D_REQUIRE(classes_per_task && heatmap && reg && height && dim && rot && nms_param && boxes && scores && labels && valid &&
+                  keep && workspace, "%s: null pointer", who);
     int max_cat = 0;
     for (int t = 0; t < kMaxTasks; ++t) {
         const bool on = t < num_tasks;
@@ -492,19 +493,18 @@ extern "C" int sgv3d_centerpoint_decode_tasks(int batch, int num_tasks, const in
         ts.rot[t] = on ? static_cast<const float *>(rot[t]) : nullptr;
         ts.vel[t] = (on && vel) ? static_cast<const float *>(vel[t]) : nullptr;
         ts.cat[t] = on ? classes_per_task[t] : 0;
-        ts.nms[t] = on ? nms_thresh[t] : 0.f;
+        ts.nms[t] = 0.f;
         if (on) {
             SGV3D_REQUIRE(ts.heat[t] && ts.reg[t] && ts.hei[t] && ts.dim[t] && ts.rot[t] && ts.cat[t] > 0,
-                          "centerpoint_decode: task %d has a null map or no class", t);
+                          "%s: task %d has a null map or no class", who, t);
             max_cat = ts.cat[t] > max_cat ? ts.cat[t] : max_cat;
         }
     }
     const int Kp = pow2_ge(max_num), Kp2 = pow2_ge(max_cat * max_num);
-    SGV3D_REQUIRE(Kp <= kMaxK && Kp2 <= 8192, "centerpoint_decode: max_num=%d x %d classes exceeds the LDS sort buffers", max_num, max_cat);
-    SGV3D_REQUIRE((long long)h * w >= max_num, "centerpoint_decode: max_num exceeds H*W");
+    SGV3D_REQUIRE(Kp <= kMaxK && Kp2 <= 8192, "%s: max_num=%d x %d classes exceeds the LDS sort buffers", who, max_num, max_cat);
+    SGV3D_REQUIRE((long long)h * w >= max_num, "%s: max_num exceeds H*W", who);
     const size_t need = sgv3d_centerpoint_decode_tasks_workspace_bytes(batch, num_tasks, max_cat, max_num);
-    if (workspace_bytes < need) return fail(SGV3D_ENOSPACE, "centerpoint_decode: workspace has %zu bytes, needs %zu", workspace_bytes, need);
-    hipStream_t st = as_stream(stream);
+    if (workspace_bytes < need) return fail(SGV3D_ENOSPACE, "%s: workspace has %zu bytes, needs %zu", who, workspace_bytes, need);
     float *cls_score = static_cast<float *>(workspace);
     int *cls_ind = reinterpret_cast<int *>(cls_score + (size_t)num_tasks * batch * max_cat * max_num);
     const long long hw = (long long)h * w;
@@ -522,6 +522,25 @@ extern "C" int sgv3d_centerpoint_decode_tasks(int batch, int num_tasks, const in
     for (int i = 0; i < 6; ++i) cfg.range[i] = post_center_range ? post_center_range[i] : 0.f;
     hipLaunchKernelGGL(merge_decode_kernel, dim3(batch, num_tasks), dim3(kTk), (sizeof(float) + sizeof(int)) * (size_t)Kp2, st, batch,
                        max_cat, h, w, max_num, Kp2, cls_score, cls_ind, ts, batch_stride, cfg, boxes, scores, labels, valid);
+    return SGV3D_OK;
+}
+
+extern "C" int sgv3d_centerpoint_decode_tasks(int batch, int num_tasks, const int32_t *classes_per_task, int h, int w, int max_num,
+                                              const void *const *heatmap, const void *const *reg, const void *const *height,
+                                              const void *const *dim, const void *const *rot, const void *const *vel,
+                                              long long batch_stride, float out_size_factor, float voxel_x, float voxel_y,
+                                              float pc_x, float pc_y, float score_threshold, const float *post_center_range,
+                                              int norm_bbox, const float *nms_thresh, int post_max_size, void *workspace,
+                                              size_t workspace_bytes, float *boxes, float *scores, int32_t *labels,
+                                              unsigned char *valid, unsigned char *keep, void *stream) {
+    hipStream_t st = as_stream(stream);
+    DecodeTasks ts;
+    const int rc = decode_candidates("centerpoint_decode", batch, num_tasks, classes_per_task, h, w, max_num, heatmap, reg, height,
+                                     dim, rot, vel, batch_stride, out_size_factor, voxel_x, voxel_y, pc_x, pc_y, score_threshold,
+                                     post_center_range, norm_bbox, nms_thresh, workspace, workspace_bytes, boxes, scores, labels, valid,
+                                     keep, st, ts);
+    if (rc != SGV3D_OK) return rc;
+    for (int t = 0; t < num_tasks; ++t) ts.nms[t] = nms_thresh[t];      // the circle radii
     if (max_num <= kNmsMaskK) {
         hipLaunchKernelGGL(circle_nms_kernel, dim3(batch, num_tasks), dim3(512), 0, st, max_num, boxes, valid, ts, post_max_size, keep);
     } else {
@@ -530,6 +549,44 @@ extern "C" int sgv3d_centerpoint_decode_tasks(int batch, int num_tasks, const in
                            post_max_size, keep);
     }
     return check_launch("centerpoint_decode");
+}
+
+extern "C" size_t sgv3d_centerpoint_decode_tasks_rotate_workspace_bytes(int batch, int num_tasks, int max_class, int max_num) {
+    const size_t front = sgv3d_centerpoint_decode_tasks_workspace_bytes(batch, num_tasks, max_class, max_num);
+    const size_t back = sgv3d_rotate_nms_workspace_bytes(batch, num_tasks, max_num);
+    return (front && back) ? (front + 255) / 256 * 256 + back : 0;
+}
+
+// nms_type='rotate': the same candidate stage, then the rotated-IoU NMS of decode_rotate.hip (three launches in total).
+// The workspace holds the candidate stage's part first, the NMS stage's behind it.
+extern "C" int sgv3d_centerpoint_decode_tasks_rotate(int batch, int num_tasks, const int32_t *classes_per_task, int h, int w,
+                                                     int max_num, const void *const *heatmap, const void *const *reg,
+                                                     const void *const *height, const void *const *dim, const void *const *rot,
+                                                     const void *const *vel, long long batch_stride, float out_size_factor,
+                                                     float voxel_x, float voxel_y, float pc_x, float pc_y, float score_threshold,
+                                                     const float *post_center_range, int norm_bbox, float nms_score_threshold,
+                                                     const float *nms_thr, int pre_max_size, int post_max_size,
+                                                     const float *limit_range, void *workspace, size_t workspace_bytes,
+                                                     float *boxes, float *scores, int32_t *labels, unsigned char *valid,
+                                                     unsigned char *keep, void *stream) {
+    SGV3D_REQUIRE(batch > 0 && num_tasks > 0 && num_tasks <= kMaxTasks && h > 0 && w > 0 && max_num > 0,
+                  "centerpoint_decode_rotate: non-positive size (or more than %d tasks)", kMaxTasks);
+    SGV3D_REQUIRE(classes_per_task && nms_thr && workspace, "centerpoint_decode_rotate: null pointer");
+    for (int t = 0; t < num_tasks; ++t) SGV3D_REQUIRE(nms_thr[t] >= 0.f, "centerpoint_decode_rotate: nms_thr[%d] is negative or NaN", t);
+    int max_cat = 0;
+    for (int t = 0; t < num_tasks; ++t) max_cat = classes_per_task[t] > max_cat ? classes_per_task[t] : max_cat;
+    const size_t need = sgv3d_centerpoint_decode_tasks_rotate_workspace_bytes(batch, num_tasks, max_cat, max_num);
+    SGV3D_REQUIRE(need > 0, "centerpoint_decode_rotate: a task without a class, or max_num=%d too large", max_num);
+    SGV3D_REQUIRE(workspace_bytes >= need, "centerpoint_decode_rotate: workspace has %zu bytes, needs %zu", workspace_bytes, need);
+    const size_t back = sgv3d_rotate_nms_workspace_bytes(batch, num_tasks, max_num), front = need - back;
+    DecodeTasks ts;
+    const int rc = decode_candidates("centerpoint_decode_rotate", batch, num_tasks, classes_per_task, h, w, max_num, heatmap, reg,
+                                     height, dim, rot, vel, batch_stride, out_size_factor, voxel_x, voxel_y, pc_x, pc_y,
+                                     score_threshold, post_center_range, norm_bbox, nms_thr, workspace, front, boxes, scores, labels,
+                                     valid, keep, as_stream(stream), ts);
+    if (rc != SGV3D_OK) return rc;
+    return sgv3d_rotate_nms(batch, num_tasks, max_num, boxes, scores, valid, nms_score_threshold, nms_thr, pre_max_size,
+                            post_max_size, limit_range, static_cast<unsigned char *>(workspace) + front, back, keep, stream);
 }
 
 extern "C" int sgv3d_centerpoint_decode(int batch, int num_class, int h, int w, int max_num, const float *heatmap,

@@ -15,7 +15,7 @@ HIP forward ("CenterHead convs fused per scale"):
   convs, writing a single NCHW [B, 70, H, W] buffer whose channel slices are the returned maps.
 Return structure is the reference's: ``tuple(task -> [dict(branch -> Tensor[B, c, H, W])])``.
 
-get_bboxes (decode + circle NMS) runs on the device (csrc/decode.hip).  get_targets / loss belong to
+get_bboxes (decode + circle or rotated-IoU NMS) runs on the device (csrc/decode.hip, decode_rotate.hip).  get_targets / loss belong to
 the training row of SURVEY.md §8(f) and are not implemented in this round (they raise).
 """
 import torch
@@ -341,8 +341,11 @@ class BEVHeightHead(HipModule):
         return (freeze(self.bbox_coder_cfg), freeze(self.test_cfg), bool(self.norm_bbox), tuple(int(v) for v in self.num_classes))
 
     def decode_device(self, preds_dicts):
-        """Device half of ``get_bboxes``: top-K / box assembly / circle NMS of every task (three launches) and the merge of
-        the tasks (one launch).  Only enqueues kernels on the current stream -- graph-capturable; ``BEVHeight``'s
+        """Device half of ``get_bboxes``: top-K / box assembly / NMS of every task (three launches) and the merge of the tasks
+        (one launch).  ``test_cfg['nms_type']`` picks the NMS: ``'circle'`` (every shipped config; ``min_radius``,
+        ``post_max_size``) or ``'rotate'`` (greedy rotated-IoU BEV NMS; ``nms_thr`` -- a scalar or one per task --,
+        ``pre_max_size``, ``post_max_size``, ``score_threshold``, ``post_center_limit_range``; DESIGN.md "Box decode:
+        nms_type='rotate'", parity with mmdet3d unpinned).  Only enqueues kernels on the current stream -- graph-capturable; ``BEVHeight``'s
         per-signature hipGraph runs it right behind the head, so that a harness calling ``get_bboxes`` on the forward's own
         output finds the boxes already decoded (``models/bev_height.py``).
 
@@ -351,7 +354,8 @@ class BEVHeightHead(HipModule):
         import ctypes
         from ... import _lib
         coder, tcfg = self.bbox_coder_cfg, self.test_cfg
-        assert tcfg.get('nms_type', 'circle') == 'circle', "only nms_type='circle' (every shipped config) is built"
+        nms_type = tcfg.get('nms_type', 'circle')
+        assert nms_type in ('circle', 'rotate'), "nms_type is 'circle' (every shipped config) or 'rotate'"
         lib = _lib.load()
         K = int(coder['max_num'])
         rng = coder.get('post_center_range')
@@ -375,22 +379,38 @@ class BEVHeightHead(HipModule):
             cats[task_id] = cat
         max_cat = max(int(c) for c in cats)
         # one scratch allocation: [T,B,K] candidates of every task (boxes | scores | labels | valid | keep) + the kernels' workspace
-        nws = lib.sgv3d_centerpoint_decode_tasks_workspace_bytes(B, T, max_cat, K)
+        rotate = nms_type == 'rotate'
+        nws = (lib.sgv3d_centerpoint_decode_tasks_rotate_workspace_bytes if rotate
+               else lib.sgv3d_centerpoint_decode_tasks_workspace_bytes)(B, T, max_cat, K)
+        assert nws > 0, f"max_num={K} is not supported by the {nms_type} decode"
         n = T * B * K
         scratch = torch.empty(n * (36 + 4 + 4 + 1 + 1) + 64 + nws, dtype=torch.uint8, device=dev)
         base = scratch.data_ptr()
         boxes, scores, labels, valid = base, base + n * 36, base + n * 40, base + n * 44
         keep = valid + n
         ws = (keep + n + 63) // 64 * 64
-        nms = (ctypes.c_float * T)(*[float(tcfg['min_radius'][t]) for t in range(T)])
-        with torch.cuda.device(dev), hip_ops.prof("centerpoint_decode"):
-            rc = lib.sgv3d_centerpoint_decode_tasks(
-                B, T, cats, H, W, K, ptrs['heatmap'], ptrs['reg'], ptrs['height'], ptrs['dim'], ptrs['rot'],
-                ptrs['vel'] if has_vel else None, bs, float(coder['out_size_factor']), float(coder['voxel_size'][0]),
-                float(coder['voxel_size'][1]), float(coder['pc_range'][0]), float(coder['pc_range'][1]),
-                float(thr) if thr is not None else float('-inf'), rng_c, 1 if self.norm_bbox else 0, nms,
-                int(tcfg['post_max_size']), ws, nws, boxes, scores, labels, valid, keep, _lib.stream_handle(dev))
-        _lib.check(rc, "sgv3d_centerpoint_decode_tasks")
+        front = (B, T, cats, H, W, K, ptrs['heatmap'], ptrs['reg'], ptrs['height'], ptrs['dim'], ptrs['rot'],
+                 ptrs['vel'] if has_vel else None, bs, float(coder['out_size_factor']), float(coder['voxel_size'][0]),
+                 float(coder['voxel_size'][1]), float(coder['pc_range'][0]), float(coder['pc_range'][1]),
+                 float(thr) if thr is not None else float('-inf'), rng_c, 1 if self.norm_bbox else 0)
+        back = (ws, nws, boxes, scores, labels, valid, keep, _lib.stream_handle(dev))
+        if rotate:
+            nt = tcfg['nms_thr']
+            nt = [float(v) for v in nt] if isinstance(nt, (list, tuple)) else [float(nt)] * T
+            assert len(nt) == T, "nms_thr is a scalar or one value per task"
+            lim = tcfg.get('post_center_limit_range')
+            lim_c = (ctypes.c_float * 6)(*[float(v) for v in lim]) if lim is not None and len(lim) else None
+            pre, post = tcfg.get('pre_max_size'), tcfg.get('post_max_size')       # (None: no cap, 0 in the C ABI)
+            with torch.cuda.device(dev), hip_ops.prof("centerpoint_decode_rotate"):
+                rc = lib.sgv3d_centerpoint_decode_tasks_rotate(
+                    *front, float(tcfg.get('score_threshold') or 0.0), (ctypes.c_float * T)(*nt), int(pre or 0), int(post or 0),
+                    lim_c, *back)
+            _lib.check(rc, "sgv3d_centerpoint_decode_tasks_rotate")
+        else:
+            nms = (ctypes.c_float * T)(*[float(tcfg['min_radius'][t]) for t in range(T)])
+            with torch.cuda.device(dev), hip_ops.prof("centerpoint_decode"):
+                rc = lib.sgv3d_centerpoint_decode_tasks(*front, nms, int(tcfg['post_max_size']), *back)
+            _lib.check(rc, "sgv3d_centerpoint_decode_tasks")
         # merge tasks (CenterHead.get_bboxes tail): per sample the kept boxes task after task, label offsets, z -= h/2
         TK = T * K
         packed = torch.empty(B * TK * 44 + B * 4, dtype=torch.uint8, device=dev)
@@ -411,8 +431,9 @@ class BEVHeightHead(HipModule):
 
     def get_bboxes(self, preds_dicts, img_metas=None, img=None, rescale=False, decoded=None):
         """mmdet3d ``CenterHead.get_bboxes`` (reached via models/bev_height.py:116-126) on the device:
-        sigmoid + top-K + box assembly + circle NMS of all tasks and their merge run as HIP kernels (the reference does the
-        NMS on the CPU through numba, with a device->host copy per task); the per-sample detection counts are the single
+        sigmoid + top-K + box assembly + NMS (circle, or rotated IoU with ``test_cfg['nms_type'] = 'rotate'``) of all tasks and
+        their merge run as HIP kernels (the reference does the NMS on the CPU through numba, with a device->host copy per
+        task); the per-sample detection counts are the single
         device->host read of the call.  ``decoded``: a ``decode_device`` buffer computed earlier for these very maps.
 
         Returns ``[[bboxes, scores, labels], ...]`` per sample; ``bboxes`` is

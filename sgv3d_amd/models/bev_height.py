@@ -87,7 +87,8 @@ class BEVHeight(nn.Module):
         self._graphs = {}               # signature -> [calls seen, GraphedForward | None | False (capture failed)]
         self._graph_suspended = 0
         self._flat, self._flat_age, self._flat_gen, self._flat_reg, self._flat_dirty = None, 0, 0, -1, True    # cached walk over the module tree (_stamp)
-        self._decoded = None            # (decode buffer, weak refs to the maps it was computed from, their version): see get_bboxes
+        self._graph_digest = None       # head.decode_digest() of the last _graphed_forward lookup
+        self._decoded = None            # (decode buffer, weak refs to the maps it was computed from, their version, the decode digest): see get_bboxes
         if checkpoint is not None:
             with open(checkpoint, "rb") as f:
                 state_dict = torch.load(f, map_location='cpu')
@@ -192,7 +193,8 @@ class BEVHeight(nn.Module):
         if graphed is not None:
             preds, decoded = graphed(self, x, mats_dict)
             # the graph decoded these maps already: remembered for a get_bboxes call on exactly these tensors, unmodified
-            self._decoded = (decoded, [weakref.ref(v) for task in preds for v in task[0].values()], tensor_version(preds[0][0]['heatmap']))
+            self._decoded = (decoded, [weakref.ref(v) for task in preds for v in task[0].values()], tensor_version(preds[0][0]['heatmap']),
+                             self._graph_digest)
             return preds
         self._decoded = None
         bev = self.backbone(x, mats_dict, timestamps, nhwc_out=True)   # NHWC buffer [B, Y, X, C]
@@ -218,6 +220,7 @@ class BEVHeight(nn.Module):
                tuple((k, tuple(v.shape), v.dtype) for k, v in sorted(mats_dict.items())),
                hip_ops.switch_state(), bool(getattr(self.backbone, 'fuse_lift_splat', False)),
                self.head.decode_digest())             # (the recorded decode bakes test_cfg / bbox_coder into kernel arguments)
+        self._graph_digest = key[-1]
         entry = self._graphs.get(key)
         if entry is None:
             self._graphs[key] = entry = [0, None]
@@ -286,13 +289,13 @@ class BEVHeight(nn.Module):
         spec, self._decoded = self._decoded, None
         if spec is None:
             return None
-        decoded, refs, version = spec
+        decoded, refs, version, digest = spec
         try:
             tensors = [v for task in preds_dicts for v in task[0].values()]
         except (TypeError, AttributeError, IndexError, KeyError):
             return None
         # (maps made under torch.inference_mode() have no version counter: in-place edits cannot be seen, so no reuse)
         if (len(tensors) != len(refs) or any(r() is not t for r, t in zip(refs, tensors)) or version is None
-                or tensor_version(tensors[0]) != version):
-            return None
+                or tensor_version(tensors[0]) != version or digest != self.head.decode_digest()):
+            return None                 # (the last: test_cfg / bbox_coder edited between the forward and get_bboxes, e.g. nms_type)
         return decoded

@@ -114,8 +114,8 @@ class GraphedForward:
       forked branch under the image backbone, joined right in front of the lift-splat gather -- rounds 4-5; graphs with parallel
       branches turned out to crash ROCm 7.2's hipGraphLaunch in long-lived processes).  The plan is rebuilt only when the voxel
       indices really changed (decided on the device);
-    * the **box decode** of the forward's own output (``BEVHeightHead.decode_device``: top-K, box assembly, circle NMS, task
-      merge), right behind the head: ``BEVHeight.get_bboxes`` on the very maps this call returned finds them decoded and only
+    * the **box decode** of the forward's own output (``BEVHeightHead.decode_device``: top-K, box assembly, the NMS that
+      ``test_cfg['nms_type']`` names, task merge), right behind the head: ``BEVHeight.get_bboxes`` on the very maps this call returned finds them decoded and only
       reads the detection counts back.
 
     Static input buffers (``imgs`` and the calibration tensors are copied in on the caller's stream, the latter as one
