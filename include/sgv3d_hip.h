@@ -170,6 +170,26 @@ int sgv3d_voxel_pooling_backward(int batch_size, int num_points, int num_channel
                                  long long sb, long long sc, long long sy, long long sx,
                                  float *grad_input, void *stream);
 
+/* Adjoint of the fused lift-splat: the backward of layers/backbones/lss_fpn.py:462-466,486 (lift) followed by
+ * ops/voxel_pooling/voxel_pooling.py:58-69 (splat) without the [B, D*P, C] lifted tensor or its gradient.
+ *   grad_prob[b, d, p]    = sum_c context[b, p, c] * G[b, v(b, d, p), c]     (0 where the point is not kept)
+ *   grad_context[b, p, c] = sum_d prob[b, d, p]    * G[b, v(b, d, p), c]     (kept d only)
+ * with v the voxel of point d*P + p, kept iff 0 <= x < X, 0 <= y < Y, 0 <= z < Z.  The kernel reads geom_xyz itself (no
+ * plan, no pos_memo).  C % 4 == 0, 4 <= C <= 256; grad_output rows 16-B aligned (pointer and sb, sy, sx multiples of 4
+ * floats, sy, sx >= 0); context / grad_context 16-B aligned.  Fixed summation order, no atomics: bitwise repeatable.
+ * A NULL output is not computed.  Workspace: sgv3d_lift_splat_backward_workspace_bytes (0 on bad sizes), 16-B aligned. */
+size_t sgv3d_lift_splat_backward_workspace_bytes(int batch_size, int num_depth, int num_pixels, int num_channels);
+int sgv3d_lift_splat_backward(int batch_size, int num_depth, int num_pixels, int num_channels,
+                              int num_voxel_x, int num_voxel_y, int num_voxel_z,
+                              const int32_t *geom_xyz,          /* [B, D*P, 3], point id = d*P + pixel */
+                              const float *prob,                /* [B, D, P]  */
+                              const float *context,             /* [B, P, C]  */
+                              const float *grad_output,         /* rows of C contiguous floats at b*sb + y*sy + x*sx */
+                              long long sb, long long sy, long long sx,
+                              float *grad_prob,                 /* [B, D, P] fully written, or NULL */
+                              float *grad_context,              /* [B, P, C] fully written, or NULL */
+                              void *workspace, size_t workspace_bytes, void *stream);
+
 /* ================================================================================================
  * Geometry (frustum -> voxel indices)
  * ================================================================================================ */

@@ -283,6 +283,83 @@ class VoxelPooling(Function):
         return None, grad_input.reshape(shape), None         # voxel_pooling.py:69
 
 
+_LSG_WORKSPACE = {}
+
+
+def lift_splat_covers(num_channels, num_cams=1):
+    """True where ``lift_splat`` (forward gather and its adjoint kernel) applies: rows of whole float4, at most 256
+    channels, one camera per sample (point id = depth * pixels + pixel)."""
+    return int(num_cams) == 1 and int(num_channels) % 4 == 0 and 4 <= int(num_channels) <= 256
+
+
+class LiftSplat(Function):
+    """``lift_splat(geom_xyz, prob, context, voxel_num)``: ``voxel_pooling(geom_xyz, prob[..., None] * context[:, None],
+    voxel_num)`` (layers/backbones/lss_fpn.py:462-466,486 + ops/voxel_pooling/voxel_pooling.py:10-72) without the lifted
+    tensor, forward (``VoxelPlan.lift_splat``) or backward (``sgv3d_lift_splat_backward``, which reads ``geom_xyz`` itself:
+    no ``pos_memo``)."""
+
+    @staticmethod
+    def forward(ctx, geom_xyz, prob, context, voxel_num):
+        assert geom_xyz.is_contiguous()                      # voxel_pooling.py:25
+        assert prob.is_contiguous() and context.is_contiguous()
+        _check_cuda(geom_xyz, "geom_xyz", torch.int32)
+        _check_cuda(prob, "prob", torch.float32)
+        _check_cuda(context, "context", torch.float32)
+        ctx.mark_non_differentiable(geom_xyz)                # voxel_pooling.py:28
+        assert prob.dim() == 3 and context.dim() == 3, "prob [B, D, P], context [B, P, C]"
+        B, D, P = (int(s) for s in prob.shape)
+        C = int(context.shape[-1])
+        assert tuple(context.shape[:2]) == (B, P)
+        if not lift_splat_covers(C):
+            raise RuntimeError(f"lift_splat: needs C % 4 == 0 and 4 <= C <= 256 (got {C})")
+        geom_xyz = geom_xyz.reshape(B, -1, geom_xyz.shape[-1])
+        assert geom_xyz.shape[1] == D * P and geom_xyz.shape[2] == 3      # voxel_pooling.py:33
+        X, Y, Z = _voxel_num_ints(voxel_num)
+        plan = VoxelPlan(geom_xyz, (X, Y, Z))
+        output_features = plan.lift_splat(prob, context)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            ctx.save_for_backward(geom_xyz, prob, context)
+            ctx.voxel_num = (X, Y, Z)
+        return output_features.permute(0, 3, 1, 2)           # voxel_pooling.py:55
+
+    @staticmethod
+    def backward(ctx, grad_output_features):
+        geom_xyz, prob, context = ctx.saved_tensors
+        X, Y, Z = ctx.voxel_num
+        B, D, P = (int(s) for s in prob.shape)
+        C = int(context.shape[-1])
+        g = grad_output_features
+        if g.dtype != torch.float32:
+            g = g.float()
+        if g.stride(1) != 1 or any(s % 4 for s in (g.stride(0), g.stride(2), g.stride(3))) or g.data_ptr() % 16:
+            g = g.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)  # one NHWC copy (an NCHW-contiguous gradient)
+        sb, _, sy, sx = (int(s) for s in g.stride())
+        grad_prob = torch.empty_like(prob) if ctx.needs_input_grad[1] else None
+        grad_context = torch.empty_like(context) if ctx.needs_input_grad[2] else None
+        lib = _lib.load()
+        nws = lib.sgv3d_lift_splat_backward_workspace_bytes(B, D, P, C)
+        ws = _LSG_WORKSPACE.get(g.device.index)
+        if ws is None or ws.numel() < nws:
+            # (reserved by the ABI, never touched by the kernel: one buffer per device instead of an allocation per step;
+            #  a buffer first needed inside a graph capture is not kept beyond the capture's pool)
+            ws = torch.empty(nws, dtype=torch.uint8, device=g.device)
+            if not torch.cuda.is_current_stream_capturing():
+                _LSG_WORKSPACE[g.device.index] = ws
+        with torch.cuda.device(g.device), hip_ops.prof("lift_splat_backward"):
+            rc = lib.sgv3d_lift_splat_backward(B, D, P, C, X, Y, Z, geom_xyz.data_ptr(), prob.data_ptr(), context.data_ptr(),
+                                               g.data_ptr(), sb, sy, sx, _lib.ptr(grad_prob), _lib.ptr(grad_context),
+                                               ws.data_ptr(), nws, _lib.stream_handle(g.device))
+        _lib.check(rc, "sgv3d_lift_splat_backward")
+        return None, grad_prob, grad_context, None
+
+
+def lift_splat(geom_xyz, prob, context, voxel_num):
+    """``lift_splat(geom_xyz [B, ..., 3] int32, prob [B, D, P], context [B, P, C], voxel_num) -> [B, C, Y, X]``: the pooled map
+    of the lifted tensor ``prob[b, d, p] * context[b, p, :]`` (point id ``d * P + p``) without building it; differentiable in
+    ``prob`` and ``context``.  Bitwise ``voxel_pooling(geom_xyz, lifted, voxel_num)`` forward; gradients in a fixed order."""
+    return LiftSplat.apply(geom_xyz, prob, context, voxel_num)
+
+
 def _voxel_pooling_inference(geom_xyz, input_features, voxel_num):
     """The operator for a call that needs no gradient, with the host work cut to what the call needs: the same checks as
     ``VoxelPooling.forward`` (voxel_pooling.py:25-33), one output allocation, ONE library call

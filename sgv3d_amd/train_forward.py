@@ -41,7 +41,7 @@ from . import misc_grad
 from .norm_grad import batch_norm_act, deferred_counters
 from .layers import blocks
 from .layers.backbones import bsm_lss_fpn, lss_fpn
-from .ops.voxel_pooling import voxel_pooling
+from .ops.voxel_pooling import get_mode, lift_splat, lift_splat_covers, voxel_pooling
 
 __all__ = ['bevheight_train_forward']
 
@@ -177,6 +177,21 @@ def heightnet(hn, x, mats_dict):
     return conv(hn.height_layer, h), context
 
 
+def _fused_splat(bb, num_cams, num_channels):
+    """The lifted tensor [B, D*P, C] and its gradient are not built (``lift_splat``: rows formed inside the gather, adjoint in
+    one kernel) -- the inference path's switch (``bb.fuse_lift_splat``, SGV3D_FUSE_LIFT_SPLAT=0), one camera per sample,
+    the planned pooling mode."""
+    return (getattr(bb, 'fuse_lift_splat', False) and num_cams == 1 and get_mode() == "planned"
+            and lift_splat_covers(num_channels, num_cams))
+
+
+def _lift_splat(bb, geom, prob, rows, B):
+    """prob NHWC [B, fH, fW, D], rows NHWC [B, fH, fW, C] -> pooled map [B, C, Y, X] (a view of NHWC)."""
+    fH, fW, D = (int(v) for v in prob.shape[1:])
+    return lift_splat(geom, prob.permute(0, 3, 1, 2).reshape(B, D, fH * fW).contiguous(),
+                      rows.reshape(B, fH * fW, int(rows.shape[-1])).contiguous(), bb._voxel_num_host)
+
+
 def lss_fpn_forward(bb, imgs, mats_dict, want_feats=False):
     """LSSFPN._forward_single_sweep for the key frame (lss_fpn.py:422-495) -> BEV map NHWC [B, Y, X, C]
     (and, with ``want_feats``, the neck features the assist layer reads, :459)."""
@@ -186,13 +201,16 @@ def lss_fpn_forward(bb, imgs, mats_dict, want_feats=False):
     feats = secondfpn(bb.img_neck, resnet(bb.img_backbone, x))
     height, context = heightnet(bb.height_net, feats, mats_dict)
     prob = height.softmax(-1)                                              # over the D height bins (:483)
-    lifted = prob.permute(0, 3, 1, 2).unsqueeze(-1) * context.unsqueeze(1)  # [BN, D, fH, fW, C] (:484-486)
     with torch.no_grad():
         geom = bb.get_geometry_voxel_index(
             mats_dict['sensor2ego_mats'][:, 0], mats_dict['sensor2virtual_mats'][:, 0], mats_dict['intrin_mats'][:, 0],
             mats_dict['ida_mats'][:, 0], mats_dict['reference_heights'][:, 0], mats_dict.get('bda_mat', None))
-    D, fH, fW, C = (int(v) for v in lifted.shape[1:])
-    bev = voxel_pooling(geom, lifted.reshape(B, N, D, fH, fW, C).contiguous(), bb._voxel_num_host)   # [B, C, Y, X] view
+    if _fused_splat(bb, N, int(context.shape[-1])):
+        bev = _lift_splat(bb, geom, prob, context, B)                      # [B, C, Y, X] view, no lifted tensor
+    else:
+        lifted = prob.permute(0, 3, 1, 2).unsqueeze(-1) * context.unsqueeze(1)  # [BN, D, fH, fW, C] (:484-486)
+        D, fH, fW, C = (int(v) for v in lifted.shape[1:])
+        bev = voxel_pooling(geom, lifted.reshape(B, N, D, fH, fW, C).contiguous(), bb._voxel_num_host)   # [B, C, Y, X] view
     return (bev.permute(0, 2, 3, 1), feats) if want_feats else bev.permute(0, 2, 3, 1)
 
 
@@ -251,13 +269,16 @@ def bsm_lss_fpn_forward(bb, imgs, mats_dict):
     C = int(tran.shape[-1])
     if C % 4:
         tran = F.pad(tran, (0, 4 - C % 4))                                 # 87 -> 88, as the inference path carries it
-    lifted = height.permute(0, 3, 1, 2).unsqueeze(-1) * tran.unsqueeze(1)  # [BN, D, fH, fW, 88] (:530)
     with torch.no_grad():
         geom = bb.get_geometry_voxel_index(
             mats_dict['sensor2ego_mats'][:, 0], mats_dict['sensor2virtual_mats'][:, 0], mats_dict['intrin_mats'][:, 0],
             mats_dict['ida_mats'][:, 0], mats_dict['reference_heights'][:, 0], mats_dict.get('bda_mat', None))
-    D, fH, fW, Cp = (int(v) for v in lifted.shape[1:])
-    bev = voxel_pooling(geom, lifted.reshape(B, N, D, fH, fW, Cp).contiguous(), bb._voxel_num_host)
+    if _fused_splat(bb, N, int(tran.shape[-1])):
+        bev = _lift_splat(bb, geom, height, tran, B)
+    else:
+        lifted = height.permute(0, 3, 1, 2).unsqueeze(-1) * tran.unsqueeze(1)  # [BN, D, fH, fW, 88] (:530)
+        D, fH, fW, Cp = (int(v) for v in lifted.shape[1:])
+        bev = voxel_pooling(geom, lifted.reshape(B, N, D, fH, fW, Cp).contiguous(), bb._voxel_num_host)
     return bev.permute(0, 2, 3, 1), (_nchw(semantic0), _nchw(semantic1))
 
 

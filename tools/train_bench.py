@@ -32,6 +32,8 @@ ap.add_argument("--clip", type=float, default=5.0, help="global gradient-norm bo
                 "exps/bevheight/dair-v2x/bev_height_lss_r50_864_1536_256x256.py:405); 0 = off")
 ap.add_argument("--bucket-mib", type=int, default=None, help="flat gradient bucket size (default train_step.DEFAULT_BUCKET_BYTES = 48 MiB)")
 ap.add_argument("--profile", action="store_true", help="per-kernel-family times of one step (HIP events, eager)")
+ap.add_argument("--no-fuse-lift-splat", action="store_true", help="lift and splat as two steps (torch mul + the voxel_pooling operator, the lifted "
+                "tensor and its gradient in HBM) instead of the fused operator ops.voxel_pooling.lift_splat")
 ap.add_argument("--checkpoint", default=None, help="after the timed steps: time save_checkpoint to this file and load_checkpoint "
                 "back into the model and optimiser (sgv3d_amd/checkpoint.py)")
 args = ap.parse_args()
@@ -51,6 +53,8 @@ if BSM:
     bconf = dict(bconf, is_train_height=True)
 torch.manual_seed(0)
 model = BEVHeight(bconf, hconf, is_train_height=BSM).to(dev).train()
+if args.no_fuse_lift_splat:
+    model.backbone.fuse_lift_splat = False
 for m in model.modules():
     if isinstance(m, torch.nn.Dropout):
         m.p = 0.0 if args.no_dropout else 0.5
@@ -152,6 +156,7 @@ out = {"metric": "training samples/s (forward + loss + backward + all-reduce + A
        "allreduce_overlapped_with_backward": not args.no_overlap, "parameters": nparam, "loss": float(loss.detach()), "config": args.config, "loss_trace": TRACE or None, "graph": bool(args.graph), "graph_replays": graphed.replays if args.graph else 0,
        "update_in_graph": bool(graphed.in_graph_update) if args.graph else None, "optimizer_steps": opt.steps,
        "peak_mem_gb": torch.cuda.max_memory_allocated(dev) / 2**30, "data": "synthetic",
+       "fuse_lift_splat": bool(model.backbone.fuse_lift_splat),
        # (a 1-rank group with SGV3D_FORCE_DIST=1 still broadcasts / all-reduces through RCCL: the single-GPU stand-in for cfg-4)
        "collectives_active": bool(opt._collectives()), "allreduces_launched_inside_backward": EARLY[0],
        "first_allreduce_launch_at_fraction_of_backward": FIRST, "bucket_mib": max(g.numel() for _, g, _ in opt.flat.buckets) * 4 / 2**20,
