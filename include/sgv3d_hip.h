@@ -1089,6 +1089,25 @@ int sgv3d_deform_im2col3x3_backward_det(int batch, int h, int w, int channels, i
                                         float *grad_offset, int grad_off_ld, void *workspace, size_t workspace_bytes,
                                         void *stream);
 
+/* Weight gradient of the deformable 3x3 convolution with the samples recomputed (csrc/dcn_grad.hip; mixed-precision training:
+ * f32 tensors, bf16 operands, f32 accumulation):
+ *   dw[g opg + co][ci][r][s] = sum over pixels p of bf16(dy[p][g opg + co]) * bf16(sample(x, p, tap 3 r + s, g cpg + ci))
+ * where the sample is formed exactly as sgv3d_deform_conv3x3_forward_bf16 forms it for f32 x (= the column tensor of
+ * sgv3d_deform_im2col3x3 rounded once to bf16): no tensor of the column size is read or written.
+ *   x f32 NHWC [B, H, W, C]; offset f32 [B, H, W, off_ld >= 18]; dy f32 [B, H, W, groups * out_per_group];
+ *   dw f32 OIHW [groups * out_per_group][C / groups][3][3], overwritten
+ *   split: pixel ranges summed separately and added in range order; 0 = a rule of the shape alone (no timing, no host
+ *          synchronisation: capturable).  Two calls give identical bits.
+ *   workspace: sgv3d_deform_conv3x3_backward_weight_bf16_workspace_bytes(...) bytes for the same shape and split (a HOST
+ *          function; 0 = shape not covered).  Too small a workspace: SGV3D_ENOSPACE, nothing launched.
+ * C/groups % 32 == 0, out_per_group % 4 == 0, groups <= 8, any B * H * W; x and dy below 2 GiB each; x, dy and the workspace
+ * 16-byte aligned.  Bad arguments are refused (SGV3D_EINVAL) before any HIP call. */
+size_t sgv3d_deform_conv3x3_backward_weight_bf16_workspace_bytes(int batch, int h, int w, int channels, int groups,
+                                                                 int out_per_group, int split);
+int sgv3d_deform_conv3x3_backward_weight_bf16(int batch, int h, int w, int channels, int groups, int out_per_group,
+                                              const float *x, const float *offset, int off_ld, const float *dy, float *dw,
+                                              int split, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ================================================================================================
  * Image preprocessing (csrc/preprocess.hip): decoded uint8 camera frames -> model input
  * ================================================================================================ */

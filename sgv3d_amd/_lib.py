@@ -202,6 +202,9 @@ _PROTOS = {
     "sgv3d_deform_im2col3x3_backward_det_workspace_bytes": (c_size_t, [c_int] * 3),
     "sgv3d_deform_im2col3x3_backward_det": (c_int, [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                                                   c_void_p, c_size_t, c_void_p]),
+    "sgv3d_deform_conv3x3_backward_weight_bf16_workspace_bytes": (c_size_t, [c_int] * 7),
+    "sgv3d_deform_conv3x3_backward_weight_bf16": (c_int, [c_int] * 6 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                                                        c_void_p, c_size_t, c_void_p]),
     "sgv3d_rotate_iou_pairs": (c_int, [c_int, c_int] + [c_void_p] * 6 + [c_int, c_int, c_void_p, c_void_p]),
     "sgv3d_kitti_eval_curves": (c_int, [c_int] + [c_void_p] * 9 + [c_int, ctypes.c_double, c_int, c_ll, c_int] + [c_void_p] * 4),
     "sgv3d_resample_coeffs": (c_int, [c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(c_int)]),

@@ -1023,7 +1023,7 @@ def switch_state():
     return tuple(g.get(k) for k in ("AUTOTUNE", "SPLIT_K", "WINOGRAD", "FUSED_HEAD", "HEAD_PATH", "MFMA_BF16", "BF16_ACTIVATIONS",
                                     "MFMA_F32X3", "MFIRST", "WINO4", "WINO_HALF", "PATCH_BF16", "DW_BF16", "DW_DEEP", "DW_NARROW",
                                     "DW_SPLIT_K", "DW_DEEP_MAX_WGS", "PAIR_BF16", "TUNE_STREAMS", "PARALLEL_BRANCHES", "F4RES", "OCC5", "WINO4_G48", "DCN_FUSED", "WINO4_X3", "PW_X3",
-                                    "DCN_FUSED_BF16"))
+                                    "DCN_FUSED_BF16", "DCN_FUSED_TRAIN"))
 
 
 def conv_pair_eligible(a, b, x, residual=None):
@@ -1265,6 +1265,11 @@ DCN_FUSED = _os.environ.get("SGV3D_DCN_FUSED", "1") != "0"     # 0: deformable i
 # of tools/dcn_probe.py bf16 (profiles/dcn_bf16_bench.json).  SGV3D_DCN_FUSED_BF16=0 keeps the im2col form in bf16
 # mode only; SGV3D_DCN_FUSED=0 switches it off together with the f32 launch.
 DCN_FUSED_BF16 = _os.environ.get("SGV3D_DCN_FUSED_BF16", "1") != "0"
+# mixed-precision TRAINING step (MFMA_BF16 with TRAIN_BF16_WGRAD, f32 tensors): the DCN is misc_grad.deform_conv3x3 -- the one-launch
+# forward above, the weight gradient with the samples recomputed (csrc/dcn_grad.hip) and the gather-form sampling adjoint in every
+# mode; no column tensor is kept.  0 (SGV3D_DCN_FUSED_TRAIN=0): im2col + one 1x1 convolution per group.  On: the graphed cfg-2 batch-2
+# step is 29.94 ms against 30.94 ms, ten times the run-to-run spread (profiles/dcn_train_step_ab.json).
+DCN_FUSED_TRAIN = _os.environ.get("SGV3D_DCN_FUSED_TRAIN", "1") != "0"
 
 
 def deform_conv3x3_eligible(x, convs):

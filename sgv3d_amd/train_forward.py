@@ -143,6 +143,10 @@ def deform_conv(d, x):
     B, H, W, C = (int(v) for v in x.shape)
     offset = conv(d.conv_offset, x)                                        # [B, H, W, 18]: (dy, dx) per tap
     g = d.groups
+    if (hip_ops.DCN_FUSED_TRAIN and hip_ops.MFMA_BF16 and not hip_ops.MFMA_F32X3 and hip_ops.TRAIN_BF16_WGRAD and hip_ops.DCN_FUSED
+            and hip_ops.DCN_FUSED_BF16 and x.dtype == torch.float32 and misc_grad.deform_conv3x3_covers(C, g, d.out_channels)):
+        # mixed-precision step: one launch forward, the weight gradient recomputes the samples -- no column tensor is kept
+        return misc_grad.deform_conv3x3(x, offset, d.weight, g)
     cpg, opg = d.in_channels // g, d.out_channels // g
     col = misc_grad.deform_im2col3x3(x, offset, g)                         # [B, H, W, g * 9 * cpg], HIP forward + adjoint
     outs = []

@@ -34,10 +34,13 @@ ap.add_argument("--bucket-mib", type=int, default=None, help="flat gradient buck
 ap.add_argument("--profile", action="store_true", help="per-kernel-family times of one step (HIP events, eager)")
 ap.add_argument("--no-fuse-lift-splat", action="store_true", help="lift and splat as two steps (torch mul + the voxel_pooling operator, the lifted "
                 "tensor and its gradient in HBM) instead of the fused operator ops.voxel_pooling.lift_splat")
+ap.add_argument("--no-fuse-dcn", action="store_true", help="the deformable convolution as im2col + one 1x1 convolution per group (the column "
+                "tensor kept for backward) instead of misc_grad.deform_conv3x3 (hip_ops.DCN_FUSED_TRAIN)")
 ap.add_argument("--checkpoint", default=None, help="after the timed steps: time save_checkpoint to this file and load_checkpoint "
                 "back into the model and optimiser (sgv3d_amd/checkpoint.py)")
 args = ap.parse_args()
 
+hip_ops.DCN_FUSED_TRAIN = not args.no_fuse_dcn
 if args.dtype == "bf16":
     hip_ops.MFMA_BF16 = True
     hip_ops.BF16_ACTIVATIONS = False        # f32 tensors between the layers (the training kernels' contract); bf16 operands only
@@ -157,6 +160,7 @@ out = {"metric": "training samples/s (forward + loss + backward + all-reduce + A
        "update_in_graph": bool(graphed.in_graph_update) if args.graph else None, "optimizer_steps": opt.steps,
        "peak_mem_gb": torch.cuda.max_memory_allocated(dev) / 2**30, "data": "synthetic",
        "fuse_lift_splat": bool(model.backbone.fuse_lift_splat),
+       "fuse_dcn": bool(hip_ops.DCN_FUSED_TRAIN and args.dtype == "bf16"),
        # (a 1-rank group with SGV3D_FORCE_DIST=1 still broadcasts / all-reduces through RCCL: the single-GPU stand-in for cfg-4)
        "collectives_active": bool(opt._collectives()), "allreduces_launched_inside_backward": EARLY[0],
        "first_allreduce_launch_at_fraction_of_backward": FIRST, "bucket_mib": max(g.numel() for _, g, _ in opt.flat.buckets) * 4 / 2**20,
