@@ -6,8 +6,9 @@
  * hipStream_t passed as void* (NULL = the null stream).  No torch types.  Every entry point only
  * ENQUEUES work on `stream` (no allocation, no synchronisation, graph-capturable) and returns
  * 0 on success or a negative SGV3D_E* code; sgv3d_last_error() gives the message for the calling
- * thread.  Nothing is retained between calls: all buffers, including workspaces, are owned by the
- * caller.
+ * thread.  All buffers, including workspaces, are owned by the caller, and the library retains nothing
+ * between calls EXCEPT the level-1 voxel plans described under sgv3d_voxel_pooling_forward (memory the
+ * library owns, freed by sgv3d_voxel_pooling_cache_clear).
  *
  * Each declaration cites the reference interface it replaces (paths relative to the reference repo).
  */
@@ -47,7 +48,7 @@ int sgv3d_abi_version(void);
  * This is the symbol the reference's own Python wrapper reaches through voxel_pooling_ext (INTEGRATION.md level 1), so it
  * carries the fast path itself: per (device, stream, sizes) it keeps a voxel plan (below) in memory the library owns.
  * Every call compares geom_xyz with the tensor the plan was built for ON THE DEVICE (the same pass writes pos_memo); while
- * it is unchanged -- a roadside camera -- the rows are summed by the deterministic gather (vp_gather3_kernel, added to
+ * it is unchanged -- a roadside camera -- the rows are summed by the deterministic gather (vp_gather_vox_kernel, added to
  * output_features, empty voxels untouched); a call whose geom_xyz differs is served by the float-atomic scatter of the
  * reference (order-nondeterministic, like the reference) and the plan is rebuilt by a later call, once the host has seen
  * the device's note -- the host never waits for the device.  Inside a stream capture with no plan yet, with channel counts
@@ -67,13 +68,18 @@ int sgv3d_voxel_pooling_forward_fresh(int batch_size, int num_points, int num_ch
                                       int num_voxel_x, int num_voxel_y, int num_voxel_z,
                                       const int32_t *geom_xyz, const float *input_features,
                                       float *output_features, int32_t *pos_memo, void *stream);
-/* Which gather kernel the planned / level-1 / fused entries launch: 0 or 2 = the voxel-owner kernel (round 4, default),
- * 1 = the slot-balanced kernel of round 3.  Both give exact sums of the same rows; their fixed summation orders differ (the
- * fused lift-splat entry and the operator always use the same one, so they stay bitwise equal).  Also SGV3D_VP_KERNEL=slot
- * at load time.  (Tests and probes; not part of the reference's interface.) */
+/* Which gather kernel the planned / level-1 / fused entries launch for 24 <= C <= 256, C % 4 == 0: 0 or 2 = the library's
+ * rule (the voxel-owner kernel vp_gather_vox_kernel; vp_gather3_kernel, slot-balanced with 64-bit addressing, when the
+ * feature or the output tensor has 4 GB or more), 1 = vp_gather3_kernel wherever the rule would pick the voxel-owner kernel:
+ * how tests and probes run the large-tensor kernel on small data.  Both give exact sums of the same rows; their fixed
+ * summation orders differ (the fused lift-splat entry and the operator always use the same one, so they stay bitwise
+ * equal).  Process-wide, read at every launch.  Other values: SGV3D_EINVAL.  (Not part of the reference's interface.) */
 int sgv3d_voxel_pooling_select_kernel(int which);
-/* the kernel those entries launch for these sizes (fused = the lift-splat form): 1 slot-balanced, 2 voxel-owner, 0 = neither
- * (channel counts outside 24 .. 256 / not a multiple of 4 take the generic gather) -- for reports (bench.py) */
+/* The kernel those entries launch for these sizes in their f32 forms, by the same rule and the current selection: 2 = the
+ * voxel-owner kernel, 0 = anything else (vp_gather3_kernel for tensors of 4 GB or more or after select_kernel(1);
+ * vp_gather_kernel for channel counts outside 24 .. 256 / not a multiple of 4).  `fused` (the lift-splat form) does not
+ * change the answer: the context tensor's pixel count is not an argument, so it is taken as large as num_points allows --
+ * 2 is never reported for a launch that cannot take the voxel-owner kernel.  For reports (bench.py). */
 int sgv3d_voxel_pooling_kernel_for(int batch_size, int num_points, int num_channels, int num_voxel_x, int num_voxel_y, int fused);
 int sgv3d_voxel_pooling_cache_clear(void);
 int sgv3d_voxel_pooling_cache_stats(unsigned long long *out4);
@@ -123,8 +129,8 @@ int sgv3d_voxel_plan_build_cached(int batch_size, int num_points,
 size_t sgv3d_voxel_plan_stats_offset(int batch_size, int num_points, int num_voxel_x, int num_voxel_y);
 
 /* output_features f32 [B, Y, X, C], fully overwritten.  Replaces the same reference kernel
- * (voxel_pooling_forward_cuda.cu:9-36) when the caller holds a plan.  One launch (vp_gather_fast_kernel: every voxel is
- * summed by one wave, rows written once, empty voxels zero-filled).  `workspace`: unused since round 3 (the round-2 gather
+ * (voxel_pooling_forward_cuda.cu:9-36) when the caller holds a plan.  One launch (vp_gather_vox_kernel: every voxel is
+ * summed by one row group, wave or workgroup, rows written once, empty voxels zero-filled).  `workspace`: unused since round 3 (the round-2 gather
  * staged partial rows there); sgv3d_voxel_pooling_workspace_bytes returns 16 and the argument may be any pointer or NULL. */
 size_t sgv3d_voxel_pooling_workspace_bytes(int batch_size, int num_points, int num_channels);
 int sgv3d_voxel_pooling_forward_planned(int batch_size, int num_points, int num_channels,

@@ -6,15 +6,18 @@
 //                            channel) so every atomic wave-instruction covers contiguous 256-B row
 //                            segments (the shape the memory-side atomic units run at full rate);
 //                            rows of dropped points are never read.
-//   2. plan build + vp_gather3_kernel   deterministic CSR formulation: count -> scan -> fill ->
-//                            per-segment sort once per calibration, then one launch gathers every output
-//                            row with 16-B loads (work cut evenly over the sorted slot list, each voxel
-//                            summed by one wave) and writes it once.  vp_gather_kernel (one wave per 4
-//                            voxels) serves channel counts the slot-balanced kernel does not cover.
-//   3. the same gather with rows formed on the fly as prob * context (FUSED; never materialises the
-//                            [B,N,C] lifted tensor), with bf16 rows / bf16 output (bf16 compute mode), and
-//                            accumulating into a caller-zeroed tensor behind the reference's own entry
-//                            point (sgv3d_voxel_pooling_forward keeps a plan per stream, "level 1").
+//   2. plan build + gather   deterministic CSR formulation: count -> scan -> fill -> per-segment sort -> voxels by population
+//                            class, once per calibration; then ONE launch gathers every output row with 16-B loads and
+//                            writes it once.  Which kernel (vp_pick_gather):
+//                              vp_gather_vox_kernel  the default (C % 4 == 0, 24 <= C <= 256, tensors below 4 GB): a row
+//                                                    group of lanes owns a whole voxel, voxels dealt by population class;
+//                              vp_gather3_kernel     the same channel counts, a feature or output tensor of 4 GB or more:
+//                                                    work cut evenly over the sorted slot list, 64-bit addressing;
+//                              vp_gather_kernel      every other channel count (one wave per 4 voxels).
+//   3. the same gather with rows formed on the fly as prob * context (FUSED; never materialises the [B,N,C] lifted tensor),
+//                            with bf16 rows / bf16 output (bf16 compute mode), and accumulating into a caller-zeroed
+//                            tensor behind the reference's own entry point (sgv3d_voxel_pooling_forward keeps a plan per
+//                            stream, "level 1").
 #include <atomic>
 #include "common.hpp"
 
@@ -945,8 +948,8 @@ __global__ __launch_bounds__(kBlock) void vp_gather_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
-// 2c. owner-computes gather ("v3", the default for C % 4 == 0, 24 <= C <= 256).  The work is cut over the SORTED SLOTS of the
-// plan, not over voxels, so every wave streams about the same number of 4C-byte rows whatever the per-voxel populations are
+// 2c. slot-balanced owner-computes gather ("v3": C % 4 == 0, 24 <= C <= 256, tensors of 4 GB or more; vp_pick_gather).  The
+// work is cut over the SORTED SLOTS of the plan, not over voxels, so every wave streams about the same number of 4C-byte rows whatever the per-voxel populations are
 // (camera frustums put 10^2..10^3 points into near voxels and none into most).  A wave looks at a WINDOW of cap = groups x ch
 // consecutive slots -- one chunk of ch <= 16 slots per LPR-lane row group, all rows of a chunk in flight at once -- that
 // starts every W_nom = cap - margin slots, and every voxel is summed by exactly ONE wave: the one whose nominal range
@@ -1020,6 +1023,18 @@ __device__ __forceinline__ void vp_emit_row(float *out, long long v, int C, int 
     }
 }
 
+// acc += row (FUSED: the row is pr * context row, the product rounded to f32 first -- the bits of the materialised lifted tensor)
+template <bool FUSED>
+__device__ __forceinline__ void vp_add_row(float4 &acc, const float4 &v, float pr) {
+    if constexpr (FUSED) {
+#pragma clang fp contract(off)      // (a fused multiply-add would skip the product's rounding)
+        const float px = pr * v.x, py = pr * v.y, pz = pr * v.z, pw = pr * v.w;
+        acc.x += px; acc.y += py; acc.z += pz; acc.w += pw;
+    } else {
+        vacc(acc, v);
+    }
+}
+
 // value of `x` held by lane `src` (any lane index per lane): one ds_bpermute per component
 __device__ __forceinline__ float4 vp_from_lane(const float4 &x, int src) {
     return make_float4(__shfl(x.x, src, 64), __shfl(x.y, src, 64), __shfl(x.z, src, 64), __shfl(x.w, src, 64));
@@ -1054,8 +1069,7 @@ __device__ __forceinline__ bool vp_sum_run_batch(float4 &acc, long long base, in
 #pragma unroll
     for (int k = 0; k < kChunkMax; ++k) {
         if (k < ch) {                                   // (rows that are not `want`'s are zeros: adding them changes nothing)
-            if constexpr (FUSED) vfma(acc, pr[k], val[k]);
-            else vacc(acc, val[k]);
+            vp_add_row<FUSED>(acc, val[k], pr[k]);
         }
     }
     return ended;
@@ -1196,8 +1210,7 @@ __global__ __launch_bounds__(kBlock) void vp_gather3_kernel(
                     cur = vox[k];
                     first_run = false;
                 }
-                if constexpr (FUSED) vfma(acc, pr[k], val[k]);
-                else vacc(acc, val[k]);
+                vp_add_row<FUSED>(acc, val[k], pr[k]);
             }
         }
         if (cur >= 0) {
@@ -1239,60 +1252,17 @@ __global__ __launch_bounds__(kBlock) void vp_gather3_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------
-// 2d. the same owner-computes gather, written for instruction count.  The generic kernel above runs ~1700 wave-instructions
-// per wave; at 11.4 waves per SIMD and 4 issue cycles per vector instruction that is 77 k cycles = 38 us on its own -- the
-// launch was issue-bound at 4.0 TB/s, not memory-bound.  Here (non-FUSED, tensors below 4 GB):
-//   * every row load / row store is a raw buffer instruction with a 32-bit offset idx * row_bytes + lane_bytes, and a dead
-//     slot (not this wave's, a long run's, outside the list) carries idx = -1 / voxel = -1, whose offset lies beyond
-//     num_records: the load returns zeros and the store is dropped by the hardware -- no predication, no 64-bit address math;
-//   * liveness is decided once, by the lanes that fetched the window's slot_voxel / order entries, and handed to the row
-//     lanes through LDS (9 ds_read_b128 instead of 34 ds_bpermute);
-//   * the segmented sum takes one wave-uniform branch per slot (any row group at a run border?) with a branch-free body.
-// The rare paths (last run longer than the window, long-run workgroups) are out of line.
+// 2d. row helpers of the voxel-owner gather (2e), written for instruction count.  The generic kernel above runs ~1700
+// wave-instructions per wave; at 11.4 waves per SIMD and 4 issue cycles per vector instruction that is 77 k cycles = 38 us on
+// its own -- the launch was issue-bound at 4.0 TB/s, not memory-bound.  For tensors below 4 GB every row load / row store is
+// a raw buffer instruction with a 32-bit offset idx * row_bytes + lane_bytes, and a dead slot (past a piece's end, a lane
+// outside the row groups) carries idx = -1 / voxel = -1, whose offset lies beyond num_records: the load returns zeros and the
+// store is dropped by the hardware -- no predication, no 64-bit address math.  Point ids travel from the lanes that fetched
+// them to the row lanes through LDS (ds_read_b128 instead of a ds_bpermute per row).
 // ------------------------------------------------------------------------------------------------
 typedef int vp_i32x4 __attribute__((ext_vector_type(4)));
 typedef float vp_f32x4 __attribute__((ext_vector_type(4)));
 typedef float vp_f32x2 __attribute__((ext_vector_type(2)));
-
-struct VpFastArgs {
-    const int *seg_start, *order, *slot_voxel, *long_list;
-    const void *feats;
-    void *out;
-    const int *gate;
-    unsigned feat_bytes, out_bytes;   // num_records of the two buffers
-    int V, C, lpr, groups, ch, w_nom, ldo, long_cap, nblk_regular, N;
-    // FUSED (lift-splat): feats = context [B, P, C] f32, rows formed on the fly as prob[point] * context[pixel of the point]
-    const float *prob;
-    int P;
-    int zero_on_gate;       // gate raised: zero the output instead of leaving it alone (vp_zero_output)
-};
-
-// FUSED: a live slot's point id becomes the row of its pixel in the context tensor, `pr` its probability (0 for dead slots).
-// Done once per slot by the lane that fetched the slot's entry (two integer divisions per window, not per row).
-template <bool FUSED, class Args>
-__device__ __forceinline__ void vp_fused_index(const Args &a, int &idx, float &pr) {
-    if constexpr (FUSED) {
-        pr = 0.f;
-        if (idx >= 0) {
-            pr = a.prob[idx];
-            const int b = (int)((unsigned)idx / (unsigned)a.N);
-            const int rem = idx - b * a.N;
-            idx = b * a.P + (int)((unsigned)rem % (unsigned)a.P);
-        }
-    }
-}
-
-// acc += row (FUSED: the row is pr * context row, the product rounded to f32 first -- the bits of the materialised lifted tensor)
-template <bool FUSED>
-__device__ __forceinline__ void vp_add_row(float4 &acc, const float4 &v, float pr) {
-    if constexpr (FUSED) {
-#pragma clang fp contract(off)      // (a fused multiply-add would skip the product's rounding)
-        const float px = pr * v.x, py = pr * v.y, pz = pr * v.z, pw = pr * v.w;
-        acc.x += px; acc.y += py; acc.z += pz; acc.w += pw;
-    } else {
-        vacc(acc, v);
-    }
-}
 
 template <bool FB>
 __device__ __forceinline__ float4 vp_buf_load_row(__amdgpu_buffer_rsrc_t rsrc, unsigned off) {
@@ -1328,269 +1298,10 @@ __device__ __forceinline__ void vp_buf_emit(__amdgpu_buffer_rsrc_t rsrc, int vox
     }
 }
 
-// Rows of the slots [base, base + groups*ch) that still belong to voxel `want` (marked or not), lean form: group g sums slots
-// base + g*ch + k (k ascending) into `acc`; the caller adds the groups' sums in ascending group order.  Returns true when
-// the run ended inside this batch.  `idw`: the wave's LDS index area.  Wave-uniform.
-template <bool FB, bool FUSED>
-__device__ __forceinline__ bool vp_fast_run_batch(float4 &acc, int base, int T, int want, int g, int cl, int ch, bool ingroup,
-                                                  int gs, const int *__restrict__ order, const int *__restrict__ slot_voxel,
-                                                  __amdgpu_buffer_rsrc_t f_rsrc, unsigned row_in, unsigned lane_in, int *idw,
-                                                  const VpFastArgs &a, float *prw) {
-    const int slot = base + g * ch + cl;
-    const bool index_lane = ingroup && cl < ch;
-    bool mine = false;
-    int my_idx = -1;
-    if (index_lane && slot < T) {
-        mine = slot_voxel[slot] == want;
-        if (mine) my_idx = order[slot];
-    }
-    const bool ended = __ballot(index_lane && !mine) != 0ull;     // (sorted by voxel: `want`'s slots are a prefix of the batch)
-    float my_pr = 0.f;
-    vp_fused_index<FUSED>(a, my_idx, my_pr);
-    if (index_lane) {
-        idw[g * kChunkMax + cl] = my_idx;
-        if constexpr (FUSED) prw[g * kChunkMax + cl] = my_pr;
-    }
-    const vp_i32x4 *ip = reinterpret_cast<const vp_i32x4 *>(idw + gs * kChunkMax);
-    int idx[kChunkMax];
-#pragma unroll
-    for (int q = 0; q < kChunkMax / 4; ++q) {
-        const vp_i32x4 t = ip[q];
-        idx[4 * q + 0] = t[0]; idx[4 * q + 1] = t[1]; idx[4 * q + 2] = t[2]; idx[4 * q + 3] = t[3];
-    }
-    float pr[kChunkMax];
-    if constexpr (FUSED) {
-        const vp_f32x4 *pp = reinterpret_cast<const vp_f32x4 *>(prw + gs * kChunkMax);
-#pragma unroll
-        for (int q = 0; q < kChunkMax / 4; ++q) {
-            const vp_f32x4 t = pp[q];
-            pr[4 * q + 0] = t[0]; pr[4 * q + 1] = t[1]; pr[4 * q + 2] = t[2]; pr[4 * q + 3] = t[3];
-        }
-    }
-    float4 val[kChunkMax];
-#pragma unroll
-    for (int k = 0; k < kChunkMax; ++k) val[k] = vp_buf_load_row<FB>(f_rsrc, (unsigned)idx[k] * row_in + lane_in);
-#pragma unroll
-    for (int k = 0; k < kChunkMax; ++k)
-        if (k < ch) vp_add_row<FUSED>(acc, val[k], FUSED ? pr[k] : 0.f);   // (rows that are not `want`'s came back as zeros)
-    return ended;
-}
-
-constexpr int kEvStride = 20;    // ints per row group in the LDS image of the window: entries cl = 0 .. ch+1 (<= 18), 16-B rows
 constexpr int kMaxGroups = 10;   // 64 lanes / LPR >= 6
 
-template <bool FB, bool OB, bool ACC, bool FUSED = false>
-__global__ __launch_bounds__(kBlock) void vp_gather_fast_kernel(const VpFastArgs a) {
-    if (a.gate != nullptr && *reinterpret_cast<const volatile int *>(a.gate) != 0) {
-        if (a.zero_on_gate) vp_zero_output(a.out, a.out_bytes);
-        return;
-    }
-    // per wave: ev[group][cl] = voxel of slot cb-1+cl if this wave sums it, else -1; idx[group][k] = its point id, else -1;
-    // one more all-dead block for the lanes that belong to no row group
-    __shared__ __attribute__((aligned(16))) int ev_s[kBlock / 64][(kMaxGroups + 1) * kEvStride];
-    __shared__ __attribute__((aligned(16))) int idx_s[kBlock / 64][(kMaxGroups + 1) * kChunkMax];
-    __shared__ float4 red[kBlock / 64][64];
-    __shared__ __attribute__((aligned(16))) float pr_s[kBlock / 64][FUSED ? (kMaxGroups + 1) * kChunkMax : 4];   // FUSED: idx's probabilities
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const int lpr = a.lpr, groups = a.groups, ch = a.ch;
-    const int g = lane / lpr;
-    const int cl = lane - g * lpr;
-    const bool ingroup = g < groups;
-    const int gs = ingroup ? g : groups;                         // LDS block of the lane: its row group, or the all-dead one
-    const int src_cl = ingroup ? cl : 0;
-    const int cap = groups * ch;
-    const int T = a.seg_start[a.V];
-    int *evw = ev_s[wid], *idw = idx_s[wid];
-    float *prw = pr_s[wid];
-    if (lane < kChunkMax) {                                      // the all-dead index block
-        idw[groups * kChunkMax + lane] = -1;
-        if constexpr (FUSED) prw[groups * kChunkMax + lane] = 0.f;
-    }
-    const unsigned row_in = (unsigned)a.C * (FB ? 2u : 4u);
-    const unsigned row_out = OB ? (unsigned)a.ldo * 2u : (unsigned)a.C * 4u;
-    const unsigned lane_in = (unsigned)cl * (FB ? 8u : 16u);
-    const unsigned lane_out = (unsigned)cl * (OB ? 8u : 16u);
-    unsigned pad_off = ~0u;
-    if constexpr (OB) {
-        if (cl < ((a.ldo - a.C) >> 2)) pad_off = (unsigned)a.C * 2u + (unsigned)cl * 8u;
-    }
-    const __amdgpu_buffer_rsrc_t f_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.feats), 0, (int)a.feat_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t o_rsrc = __builtin_amdgcn_make_buffer_rsrc(a.out, 0, (int)a.out_bytes, 0x00020000);
-    // ---------------------------------------------------------------- long runs: one workgroup per voxel at a time
-    if ((int)blockIdx.x >= a.nblk_regular) {
-        const int n_long = min(a.long_list[0], a.long_cap);
-        const int stride = (int)gridDim.x - a.nblk_regular;
-        for (int i = (int)blockIdx.x - a.nblk_regular; i < n_long; i += stride) {      // block-uniform trip count
-            const int v = a.long_list[1 + i];
-            const int b = a.seg_start[v], e = a.seg_start[v + 1];
-            float4 racc = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int base = b + wid * cap; base < e; base += (kBlock / 64) * cap)
-                vp_fast_run_batch<FB, FUSED>(racc, base, e, ~v, g, cl, ch, ingroup, gs, a.order, a.slot_voxel, f_rsrc, row_in, lane_in, idw, a, prw);
-            float4 wsum = make_float4(0.f, 0.f, 0.f, 0.f);
-            for (int g2 = 0; g2 < groups; ++g2) vacc(wsum, vp_from_lane(racc, g2 * lpr + src_cl));
-            if (g == 0) red[wid][cl] = wsum;
-            __syncthreads();
-            if (wid == 0) {
-                float4 tot = red[0][src_cl];
-#pragma unroll
-                for (int w = 1; w < kBlock / 64; ++w) vacc(tot, red[w][src_cl]);
-                vp_buf_emit<OB, ACC>(o_rsrc, g == 0 ? v : -1, row_out, lane_out, pad_off, tot);
-            }
-            __syncthreads();
-        }
-        return;
-    }
-    const int wave = (int)blockIdx.x * (kBlock / 64) + wid;
-
-    // ---------------------------------------------------------------- rows of empty voxels (not in ACC mode)
-    if constexpr (!ACC) {
-        const int ngroups = a.nblk_regular * (kBlock / 64) * groups;
-        const int per = (a.V + ngroups - 1) / ngroups;
-        const int v0 = (wave * groups + (ingroup ? g : 0)) * per;
-        for (int i = 0; i < per; ++i) {                           // uniform trip count
-            const int v = v0 + i;
-            int vz = -1;
-            if (ingroup && v < a.V && a.seg_start[v] == a.seg_start[v + 1]) vz = v;
-            vp_buf_emit<OB, false>(o_rsrc, vz, row_out, lane_out, pad_off, make_float4(0.f, 0.f, 0.f, 0.f));
-        }
-    }
-    const int s0 = wave * a.w_nom;
-    if (s0 >= T) return;                                         // wave-uniform
-    const int cb = s0 + g * ch;
-    // ---------------------------------------------------------------- the window's entries: lane cl of a group holds slot cb-1+cl
-    const int my_slot = cb - 1 + cl;
-    int my_vox = INT_MIN, my_idx = -1;
-    if (ingroup && cl < ch + 2 && my_slot >= 0 && my_slot < T) {
-        my_vox = a.slot_voxel[my_slot];
-        my_idx = a.order[my_slot];
-    }
-    const int up_vox = __shfl_up(my_vox, 1, 64);
-    const bool in_window = ingroup && cl >= 1 && (cl <= ch || (cl == ch + 1 && g == groups - 1));
-    const unsigned long long start_m = __ballot(in_window && my_vox != up_vox);
-    const unsigned long long nominal_m = __ballot(in_window && my_slot < s0 + a.w_nom);
-    const unsigned long long own_m = start_m & nominal_m;
-    if (own_m == 0ull) return;                                   // one voxel covers the whole range: its owner sums it
-    const int first_lane = __ffsll((long long)own_m) - 1;
-    const int first = s0 + (first_lane / lpr) * ch + (first_lane % lpr) - 1;
-    const unsigned long long tail_start_m = start_m & ~nominal_m;
-    int endw = s0 + cap;
-    if (tail_start_m != 0ull) {
-        const int end_lane = __ffsll((long long)tail_start_m) - 1;
-        endw = s0 + (end_lane / lpr) * ch + (end_lane % lpr) - 1;
-    }
-    // (slots outside the list hold INT_MIN.)  The slot right behind the window counts as live when no run starts in the tail of
-    // the window: the chunk before it then sees its last run continue and hands it to the extension loop below
-    const bool live = my_vox >= 0 && my_slot >= first && (my_slot < endw || (tail_start_m == 0ull && my_slot == s0 + cap));
-    int row_idx = live ? my_idx : -1;
-    float my_pr = 0.f;
-    vp_fused_index<FUSED>(a, row_idx, my_pr);
-    if (ingroup && cl < ch + 2) {
-        evw[g * kEvStride + cl] = live ? my_vox : -1;
-        if (cl >= 1 && cl <= ch) {
-            idw[g * kChunkMax + cl - 1] = row_idx;
-            if constexpr (FUSED) prw[g * kChunkMax + cl - 1] = my_pr;
-        }
-    }
-    if (lane < kEvStride) evw[groups * kEvStride + lane] = -1;   // the all-dead block
-    // ---------------------------------------------------------------- all rows of the chunk in flight
-    float4 val[kChunkMax];
-    float pr[kChunkMax];
-    if constexpr (FUSED) {
-        const vp_f32x4 *pp = reinterpret_cast<const vp_f32x4 *>(prw + gs * kChunkMax);
-#pragma unroll
-        for (int q = 0; q < kChunkMax / 4; ++q) {
-            const vp_f32x4 t = pp[q];
-            pr[4 * q + 0] = t[0]; pr[4 * q + 1] = t[1]; pr[4 * q + 2] = t[2]; pr[4 * q + 3] = t[3];
-        }
-    }
-    {
-        const vp_i32x4 *ip = reinterpret_cast<const vp_i32x4 *>(idw + gs * kChunkMax);
-        int idx[kChunkMax];
-#pragma unroll
-        for (int q = 0; q < kChunkMax / 4; ++q) {
-            const vp_i32x4 t = ip[q];
-            idx[4 * q + 0] = t[0]; idx[4 * q + 1] = t[1]; idx[4 * q + 2] = t[2]; idx[4 * q + 3] = t[3];
-        }
-#pragma unroll
-        for (int k = 0; k < kChunkMax; ++k)                       // (entries k >= ch are stale: never added below)
-            val[k] = vp_buf_load_row<FB>(f_rsrc, (unsigned)idx[k] * row_in + lane_in);
-    }
-    int ev[kEvStride];
-    {
-        const vp_i32x4 *ep = reinterpret_cast<const vp_i32x4 *>(evw + gs * kEvStride);
-#pragma unroll
-        for (int q = 0; q < kEvStride / 4; ++q) {
-            const vp_i32x4 t = ep[q];
-            ev[4 * q + 0] = t[0]; ev[4 * q + 1] = t[1]; ev[4 * q + 2] = t[2]; ev[4 * q + 3] = t[3];
-        }
-    }
-    // ---------------------------------------------------------------- segmented sum of the chunk: ev[1 + k] is slot k's voxel
-    float4 head = make_float4(0.f, 0.f, 0.f, 0.f), acc = head;
-    const bool before = ev[0] == ev[1] && ev[1] >= 0;            // the first run began in the previous chunk of this wave
-    bool first_run = true, has_head = false;
-#pragma unroll
-    for (int k = 0; k < kChunkMax; ++k) {
-        if (k < ch) {                                            // uniform
-            if (k > 0) {
-                const bool bnd = ev[k + 1] != ev[k];             // the run of slot k-1 ended
-                if (__ballot(bnd) != 0ull) {                     // wave-uniform branch, branch-free body
-                    const bool to_head = bnd && first_run && before;
-                    head.x = to_head ? acc.x : head.x; head.y = to_head ? acc.y : head.y;
-                    head.z = to_head ? acc.z : head.z; head.w = to_head ? acc.w : head.w;
-                    has_head = has_head || to_head;
-                    vp_buf_emit<OB, ACC>(o_rsrc, (bnd && !to_head) ? ev[k] : -1, row_out, lane_out, pad_off, acc);
-                    acc.x = bnd ? 0.f : acc.x; acc.y = bnd ? 0.f : acc.y; acc.z = bnd ? 0.f : acc.z; acc.w = bnd ? 0.f : acc.w;
-                    first_run = first_run && !bnd;
-                }
-            }
-            vp_add_row<FUSED>(acc, val[k], FUSED ? pr[k] : 0.f);
-        }
-    }
-    // the chunk's last run: slot ch-1 is ev[ch]; the slot behind the chunk ev[ch + 1] (ch is uniform but not a constant:
-    // read the two entries back from LDS instead of indexing the register array dynamically)
-    const int last_vox = evw[gs * kEvStride + ch];
-    const int next_vox = evw[gs * kEvStride + ch + 1];
-    const bool after = next_vox == last_vox && last_vox >= 0;    // continues in the next chunk / behind the window
-    const bool last_is_head = first_run && before;
-    bool single = false, has_tail = false;
-    float4 tail = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (last_is_head) { head = acc; has_head = true; single = after; }
-    else if (after) { tail = acc; has_tail = true; }
-    vp_buf_emit<OB, ACC>(o_rsrc, (!last_is_head && !after) ? last_vox : -1, row_out, lane_out, pad_off, acc);
-    // ---------------------------------------------------------------- stitch the runs cut by chunk borders (ascending chunks)
-    const unsigned long long head_m = __ballot(ingroup && has_head && cl == 0);
-    const unsigned long long single_m = __ballot(ingroup && single && cl == 0);
-    const unsigned long long tail_m = __ballot(ingroup && has_tail && cl == 0);
-    if ((head_m | tail_m) == 0ull) return;                        // wave-uniform
-    float4 carry = make_float4(0.f, 0.f, 0.f, 0.f);
-    int carry_vox = -1;
-    for (int g2 = 0; g2 < groups; ++g2) {
-        const int l0 = g2 * lpr;
-        if ((head_m >> l0) & 1ull) {
-            vacc(carry, vp_from_lane(head, l0 + src_cl));
-            if (!((single_m >> l0) & 1ull)) {                     // the run ends in this chunk: its row is complete
-                vp_buf_emit<OB, ACC>(o_rsrc, g == 0 ? carry_vox : -1, row_out, lane_out, pad_off, carry);
-                carry_vox = -1;
-            }
-        }
-        if ((tail_m >> l0) & 1ull) {
-            carry = vp_from_lane(tail, l0 + src_cl);
-            carry_vox = evw[g2 * kEvStride + ch];                 // (uniform address: that chunk's last voxel)
-        }
-    }
-    if (carry_vox < 0) return;
-    // ---------------------------------------------------------------- the last run goes on behind the window (<= kLongRun slots)
-    float4 eacc = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int base = s0 + cap; base < T; base += cap)
-        if (vp_fast_run_batch<FB, FUSED>(eacc, base, T, carry_vox, g, cl, ch, ingroup, gs, a.order, a.slot_voxel, f_rsrc, row_in, lane_in, idw, a, prw))
-            break;
-    for (int g2 = 0; g2 < groups; ++g2) vacc(carry, vp_from_lane(eacc, g2 * lpr + src_cl));
-    vp_buf_emit<OB, ACC>(o_rsrc, g == 0 ? carry_vox : -1, row_out, lane_out, pad_off, carry);
-}
-
 // ------------------------------------------------------------------------------------------------
-// 2e. voxel-owner gather (round 4).  The slot-balanced kernel above spends ~20 wave-instructions per slot on the
+// 2e. voxel-owner gather (round 4, the default).  The slot-balanced kernel (2c) spends ~20 wave-instructions per slot on the
 // book-keeping of runs that start and end anywhere inside a wave's window (ballots, per-slot boundary selects, stitching);
 // it is issue-bound -- harmless for the operator, whose rows come from HBM, but the fused lift-splat form reads its rows from
 // the L2-resident context map and ran at 0.15 of its byte roofline.  Here NOTHING is cut at arbitrary places: the plan lists
@@ -1604,11 +1315,11 @@ __global__ __launch_bounds__(kBlock) void vp_gather_fast_kernel(const VpFastArgs
 //                                     four wave sums meet in LDS and are added in wave order.
 // Fixed association per (population, channel count) => bit-reproducible.  Work is dealt with a static stride over a grid that
 // is resident at once (perm goes from the largest class to the smallest, so every wave gets the same mix and the largest
-// voxels start first); rows of empty voxels are zeroed by a walk over contiguous voxel ranges.  All loops are bounded by
+// voxels start first); the rows of empty voxels, perm's tail, are zeroed by the same launch.  All loops are bounded by
 // counts read from the plan, every wave reaches the end of the kernel.
 // ------------------------------------------------------------------------------------------------
 struct VpVoxArgs {
-    const int *order, *cls, *seg_start;     // cls[c] = number of voxels in population classes above c (vp_class)
+    const int *order, *cls;     // cls[c] = number of voxels in population classes above c (vp_class)
     const int4 *perm;       // {voxel, first slot, end slot, 0} by descending population
     const void *feats;
     void *out;
@@ -1619,7 +1330,6 @@ struct VpVoxArgs {
     int P;
     unsigned magN, magP;    // exact division of a point id (< 2^31) by N / P: umulhi(id, mag) >> sh (vp_magic)
     int shN, shP;
-    int dbg;                // SGV3D_VP_DEBUG probe bits (launch_gather)
     int zero_on_gate;       // gate raised: zero the output instead of leaving it alone (vp_zero_output)
 };
 
@@ -1645,13 +1355,15 @@ VpMagic vp_magic(int d) {
 __device__ __forceinline__ int vp_fast_div(int n, int d, unsigned mag, int sh) {
     return d == 1 ? n : (int)(__umulhi((unsigned)n, mag) >> sh);
 }
+// rows in flight per lane: 16 (90 - 112 VGPRs, 4 - 5 waves per SIMD); 8 (58 - 74 VGPRs, 6 - 8 waves per SIMD) measured within 1 us
+constexpr int kVoxRows = 16;
 constexpr int kVoxGrid = 1024;   // workgroups of the smallest launch (4 per CU); larger problems take 2 x / 4 x (launch_gather)
 
-// acc += rows of the slots [pb, pe) in slot order, `vb` <= VB at a time; `maxlen` >= pe - pb is wave-uniform (the longest piece
-// of the wave), slots past a group's own end are dead (index -1: the load returns zeros).  What bounds this loop is its
+// acc += rows of the slots [pb, pe) in slot order, `vb` <= kVoxRows at a time; `maxlen` >= pe - pb is wave-uniform (the longest
+// piece of the wave), slots past a group's own end are dead (index -1: the load returns zeros).  What bounds this loop is its
 // chain of dependent loads (slot -> point id -> row): the probabilities of the fused form are requested BEFORE the rows and
 // waited for after the rows are in flight, so they add no round trip.
-template <bool FB, bool FUSED, int VB>
+template <bool FB, bool FUSED>
 __device__ __forceinline__ void vp_vox_piece(float4 &acc, int pb, int pe, int maxlen, int cl, bool ingroup, int g, int gs, int vb,
                                              __amdgpu_buffer_rsrc_t f_rsrc, unsigned row_in, unsigned lane_in, int *idw,
                                              float *prw, const VpVoxArgs &a) {
@@ -1670,46 +1382,46 @@ __device__ __forceinline__ void vp_vox_piece(float4 &acc, int pb, int pe, int ma
                 my_row = b * a.P + rem - vp_fast_div(rem, a.P, a.magP, a.shP) * a.P;
             }
         }
-        if (index_lane) idw[g * VB + cl] = my_row;
-        const vp_i32x4 *ip = reinterpret_cast<const vp_i32x4 *>(idw + gs * VB);
-        int idx[VB];
+        if (index_lane) idw[g * kVoxRows + cl] = my_row;
+        const vp_i32x4 *ip = reinterpret_cast<const vp_i32x4 *>(idw + gs * kVoxRows);
+        int idx[kVoxRows];
 #pragma unroll
-        for (int q = 0; q < VB / 4; ++q) {
+        for (int q = 0; q < kVoxRows / 4; ++q) {
             const vp_i32x4 t = ip[q];
             idx[4 * q + 0] = t[0]; idx[4 * q + 1] = t[1]; idx[4 * q + 2] = t[2]; idx[4 * q + 3] = t[3];
         }
-        float4 val[VB];
+        float4 val[kVoxRows];
 #pragma unroll
-        for (int k = 0; k < VB; ++k) val[k] = vp_buf_load_row<FB>(f_rsrc, (a.dbg & 4) ? ~0u - 64u : (unsigned)idx[k] * row_in + lane_in);
-        float pr[VB];
+        for (int k = 0; k < kVoxRows; ++k) val[k] = vp_buf_load_row<FB>(f_rsrc, (unsigned)idx[k] * row_in + lane_in);
+        float pr[kVoxRows];
         if constexpr (FUSED) {
-            if (index_lane) prw[g * VB + cl] = my_pr;
-            const vp_f32x4 *pp = reinterpret_cast<const vp_f32x4 *>(prw + gs * VB);
+            if (index_lane) prw[g * kVoxRows + cl] = my_pr;
+            const vp_f32x4 *pp = reinterpret_cast<const vp_f32x4 *>(prw + gs * kVoxRows);
 #pragma unroll
-            for (int q = 0; q < VB / 4; ++q) {
+            for (int q = 0; q < kVoxRows / 4; ++q) {
                 const vp_f32x4 t = pp[q];
                 pr[4 * q + 0] = t[0]; pr[4 * q + 1] = t[1]; pr[4 * q + 2] = t[2]; pr[4 * q + 3] = t[3];
             }
         }
         const int n = min(vb, maxlen - base);                    // (entries k >= vb stay dead: never written, never added)
 #pragma unroll
-        for (int k = 0; k < VB; ++k)
+        for (int k = 0; k < kVoxRows; ++k)
             if (k < n) vp_add_row<FUSED>(acc, val[k], FUSED ? pr[k] : 0.f);
     }
 }
 
-// J small voxels per row group in ONE batch of VB slots: voxel j of the group owns the slots [j W, (j + 1) W), W = VB / J, of the
-// batch (populations <= W).  Four in ten non-empty voxels of cfg-2 (six in ten on cfg-3's 0.2 m grid) hold at most four points:
+// J small voxels per row group in ONE batch of kVoxRows slots: voxel j of the group owns the slots [j W, (j + 1) W),
+// W = kVoxRows / J, of the batch (populations <= W).  Four in ten non-empty voxels of cfg-2 (six in ten on cfg-3's 0.2 m grid) hold at most four points:
 // a batch per voxel would run the loads, the index exchange and the emit for one to four rows.  perm[lo .. hi) in descending
 // population; item i of the wave = voxels lo + (i groups + g) J + j.
-template <bool FB, bool OB, bool ACC, bool FUSED, int VB, int J>
+template <bool FB, bool OB, bool ACC, bool FUSED, int J>
 __device__ __forceinline__ void vp_vox_small(int lo, int hi, int gw, int nwaves, int cl, bool ingroup, int g, int gs, int groups, int lpr,
                                              __amdgpu_buffer_rsrc_t f_rsrc, __amdgpu_buffer_rsrc_t o_rsrc, unsigned row_in,
-                                             unsigned lane_in, unsigned row_out, unsigned lane_out, unsigned pad_off, int kill,
+                                             unsigned lane_in, unsigned row_out, unsigned lane_out, unsigned pad_off,
                                              int *idw, float *prw, const VpVoxArgs &a) {
-    constexpr int W = VB / J;
+    constexpr int W = kVoxRows / J;
     const int n_items = (hi - lo + groups * J - 1) / (groups * J);
-    const int myj = cl / W, myo = cl - myj * W;                   // (index lanes: cl < VB)
+    const int myj = cl / W, myo = cl - myj * W;                   // (index lanes: cl < kVoxRows)
     for (int i = gw; i < n_items; i += nwaves) {                  // wave-uniform
         int vox[J], pb = 0, pe = 0, lenmax = 0;
 #pragma unroll
@@ -1724,7 +1436,7 @@ __device__ __forceinline__ void vp_vox_small(int lo, int hi, int gw, int nwaves,
         const int n = min(W, vp_group_max(lenmax, lpr, groups)); // the largest population of the item
         const int slot = pb + myo;
         int my_idx = -1;
-        if (ingroup && cl < VB && slot < pe) my_idx = a.order[slot];
+        if (ingroup && cl < kVoxRows && slot < pe) my_idx = a.order[slot];
         float my_pr = 0.f;
         int my_row = my_idx;
         if constexpr (FUSED) {
@@ -1735,23 +1447,23 @@ __device__ __forceinline__ void vp_vox_small(int lo, int hi, int gw, int nwaves,
                 my_row = b * a.P + rem - vp_fast_div(rem, a.P, a.magP, a.shP) * a.P;
             }
         }
-        if (ingroup && cl < VB) idw[g * VB + cl] = my_row;
-        const vp_i32x4 *ip = reinterpret_cast<const vp_i32x4 *>(idw + gs * VB);
-        int idx[VB];
+        if (ingroup && cl < kVoxRows) idw[g * kVoxRows + cl] = my_row;
+        const vp_i32x4 *ip = reinterpret_cast<const vp_i32x4 *>(idw + gs * kVoxRows);
+        int idx[kVoxRows];
 #pragma unroll
-        for (int q = 0; q < VB / 4; ++q) {
+        for (int q = 0; q < kVoxRows / 4; ++q) {
             const vp_i32x4 t = ip[q];
             idx[4 * q + 0] = t[0]; idx[4 * q + 1] = t[1]; idx[4 * q + 2] = t[2]; idx[4 * q + 3] = t[3];
         }
-        float4 val[VB];
+        float4 val[kVoxRows];
 #pragma unroll
-        for (int k = 0; k < VB; ++k) val[k] = vp_buf_load_row<FB>(f_rsrc, (a.dbg & 4) ? ~0u - 64u : (unsigned)idx[k] * row_in + lane_in);
-        float pr[VB];
+        for (int k = 0; k < kVoxRows; ++k) val[k] = vp_buf_load_row<FB>(f_rsrc, (unsigned)idx[k] * row_in + lane_in);
+        float pr[kVoxRows];
         if constexpr (FUSED) {
-            if (ingroup && cl < VB) prw[g * VB + cl] = my_pr;
-            const vp_f32x4 *pp = reinterpret_cast<const vp_f32x4 *>(prw + gs * VB);
+            if (ingroup && cl < kVoxRows) prw[g * kVoxRows + cl] = my_pr;
+            const vp_f32x4 *pp = reinterpret_cast<const vp_f32x4 *>(prw + gs * kVoxRows);
 #pragma unroll
-            for (int q = 0; q < VB / 4; ++q) {
+            for (int q = 0; q < kVoxRows / 4; ++q) {
                 const vp_f32x4 t = pp[q];
                 pr[4 * q + 0] = t[0]; pr[4 * q + 1] = t[1]; pr[4 * q + 2] = t[2]; pr[4 * q + 3] = t[3];
             }
@@ -1762,19 +1474,19 @@ __device__ __forceinline__ void vp_vox_small(int lo, int hi, int gw, int nwaves,
 #pragma unroll
             for (int o = 0; o < W; ++o)
                 if (o < n) vp_add_row<FUSED>(acc, val[j * W + o], FUSED ? pr[j * W + o] : 0.f);
-            vp_buf_emit<OB, ACC>(o_rsrc, vox[j] | kill, row_out, lane_out, pad_off, acc);
+            vp_buf_emit<OB, ACC>(o_rsrc, vox[j], row_out, lane_out, pad_off, acc);
         }
     }
 }
 
-template <bool FB, bool OB, bool ACC, bool FUSED, int VB>
+template <bool FB, bool OB, bool ACC, bool FUSED>
 __global__ __launch_bounds__(kBlock) void vp_gather_vox_kernel(const VpVoxArgs a) {
     if (a.gate != nullptr && *reinterpret_cast<const volatile int *>(a.gate) != 0) {
         if (a.zero_on_gate) vp_zero_output(a.out, a.out_bytes);
         return;
     }
-    __shared__ __attribute__((aligned(16))) int idx_s[kBlock / 64][kMaxGroups * VB];
-    __shared__ __attribute__((aligned(16))) float pr_s[kBlock / 64][FUSED ? kMaxGroups * VB : 4];
+    __shared__ __attribute__((aligned(16))) int idx_s[kBlock / 64][kMaxGroups * kVoxRows];
+    __shared__ __attribute__((aligned(16))) float pr_s[kBlock / 64][FUSED ? kMaxGroups * kVoxRows : 4];
     __shared__ float4 red[kBlock / 64][64];
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
@@ -1788,8 +1500,8 @@ __global__ __launch_bounds__(kBlock) void vp_gather_vox_kernel(const VpVoxArgs a
     const int src_cl = ingroup ? cl : 0;
     int *idw = idx_s[wid];
     float *prw = pr_s[wid];
-    if (vb < VB) {                                               // (narrow rows only: entries k >= vb are never rewritten: dead)
-        for (int i = lane; i < groups * VB; i += 64) {
+    if (vb < kVoxRows) {                                         // (narrow rows only: entries k >= vb are never rewritten: dead)
+        for (int i = lane; i < groups * kVoxRows; i += 64) {
             idw[i] = -1;
             if constexpr (FUSED) prw[i] = 0.f;
         }
@@ -1810,47 +1522,28 @@ __global__ __launch_bounds__(kBlock) void vp_gather_vox_kernel(const VpVoxArgs a
     const int n_mid_end = a.cls[32];                             // perm[0 .. n_mid_end): populations above 32 (up to 32: one row group)
     const int n_long = a.cls[31 + groups];                       // perm[0 .. n_long): above 32 * groups (classes step by 32 up to 320)
     const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int kill = (a.dbg & 2) ? -1 : 0;                      // (probe: v | kill = -1 drops every row store)
-    // populations 1 .. 4 and 5 .. 8 share a batch (four / two voxels per row group) when the batch has 16 slots
-    const bool pack = VB == 16 && vb == 16 && !(a.dbg & 16);
+    // populations 1 .. 4 and 5 .. 8 share a batch (four / two voxels per row group) when the batch has 16 slots (rows of fewer
+    // than 64 channels have fewer index lanes than that: one voxel per row group)
+    const bool pack = vb == kVoxRows;
     const int n8 = pack ? a.cls[8] : nonempty;                    // perm[n_mid_end .. n8): 9 .. 32 points (one voxel per row group)
     const int n4 = pack ? a.cls[4] : nonempty;                    // perm[n8 .. n4): 5 .. 8 points; perm[n4 .. nonempty): 1 .. 4
     // ---------------------------------------------------------------- rows of empty voxels (not in ACC mode)
-    if (!ACC && !(a.dbg & 1)) {
+    if constexpr (!ACC) {
         // perm's tail lists the empty voxels (in voxel order): eight records in flight per row group, then eight row stores.
         // (The alternative -- every row group walks a contiguous range of voxel ids and zeroes the empty ones it finds in
         // seg_start -- measured equal or slower everywhere but the fused form on cfg-3's grid, by 4 %.)
         constexpr int EU = 8;
-        const int ngr = nwaves * groups;
-        const int per = (a.V + ngr - 1) / ngr;
-        const int v0 = (gw * groups + (ingroup ? g : 0)) * per;
-        if (!(a.dbg & 8)) {                                       // the zero rows from perm's tail (probe bit 8: the walk below)
-            const int n_rows = (a.V - nonempty + groups - 1) / groups;
-            for (int i0 = gw * EU; i0 < n_rows; i0 += nwaves * EU) {
-                int v[EU];
-#pragma unroll
-                for (int u = 0; u < EU; ++u) {
-                    const int vi = nonempty + (i0 + u) * groups + g;
-                    v[u] = -1;
-                    if (ingroup && i0 + u < n_rows && vi < a.V) v[u] = a.perm[vi].x;
-                }
-#pragma unroll
-                for (int u = 0; u < EU; ++u) vp_buf_emit<OB, false>(o_rsrc, v[u], row_out, lane_out, pad_off, zero4);
-            }
-        } else
-        for (int i0 = 0; i0 < per; i0 += EU) {                    // uniform trip count
-            int s[EU + 1];
-#pragma unroll
-            for (int u = 0; u <= EU; ++u) {
-                const int v = v0 + i0 + u;
-                s[u] = v <= a.V ? a.seg_start[v] : 0;
-            }
+        const int n_rows = (a.V - nonempty + groups - 1) / groups;
+        for (int i0 = gw * EU; i0 < n_rows; i0 += nwaves * EU) {
+            int v[EU];
 #pragma unroll
             for (int u = 0; u < EU; ++u) {
-                const int v = v0 + i0 + u;
-                const bool emp = ingroup && i0 + u < per && v < a.V && s[u] == s[u + 1];
-                vp_buf_emit<OB, false>(o_rsrc, emp ? v : -1, row_out, lane_out, pad_off, zero4);
+                const int vi = nonempty + (i0 + u) * groups + g;
+                v[u] = -1;
+                if (ingroup && i0 + u < n_rows && vi < a.V) v[u] = a.perm[vi].x;
             }
+#pragma unroll
+            for (int u = 0; u < EU; ++u) vp_buf_emit<OB, false>(o_rsrc, v[u], row_out, lane_out, pad_off, zero4);
         }
     }
 
@@ -1869,7 +1562,7 @@ __global__ __launch_bounds__(kBlock) void vp_gather_vox_kernel(const VpVoxArgs a
             pe = min(pb + psz, e);
         }
         float4 acc = zero4;
-        vp_vox_piece<FB, FUSED, VB>(acc, pb, pe, psz, cl, ingroup, g, gs, vb, f_rsrc, row_in, lane_in, idw, prw, a);
+        vp_vox_piece<FB, FUSED>(acc, pb, pe, psz, cl, ingroup, g, gs, vb, f_rsrc, row_in, lane_in, idw, prw, a);
         float4 wsum = zero4;
         for (int g2 = 0; g2 < groups; ++g2) vacc(wsum, vp_from_lane(acc, g2 * lpr + src_cl));
         if (g == 0) red[wid][cl] = wsum;
@@ -1878,7 +1571,7 @@ __global__ __launch_bounds__(kBlock) void vp_gather_vox_kernel(const VpVoxArgs a
             float4 tot = red[0][src_cl];
 #pragma unroll
             for (int w = 1; w < kBlock / 64; ++w) vacc(tot, red[w][src_cl]);
-            vp_buf_emit<OB, ACC>(o_rsrc, (g == 0 ? v : -1) | kill, row_out, lane_out, pad_off, tot);
+            vp_buf_emit<OB, ACC>(o_rsrc, g == 0 ? v : -1, row_out, lane_out, pad_off, tot);
         }
         __syncthreads();
     }
@@ -1894,10 +1587,10 @@ __global__ __launch_bounds__(kBlock) void vp_gather_vox_kernel(const VpVoxArgs a
             pe = min(pb + psz, e);
         }
         float4 acc = zero4;
-        vp_vox_piece<FB, FUSED, VB>(acc, pb, pe, psz, cl, ingroup, g, gs, vb, f_rsrc, row_in, lane_in, idw, prw, a);
+        vp_vox_piece<FB, FUSED>(acc, pb, pe, psz, cl, ingroup, g, gs, vb, f_rsrc, row_in, lane_in, idw, prw, a);
         float4 tot = zero4;
         for (int g2 = 0; g2 < groups; ++g2) vacc(tot, vp_from_lane(acc, g2 * lpr + src_cl));
-        vp_buf_emit<OB, ACC>(o_rsrc, (g == 0 ? v : -1) | kill, row_out, lane_out, pad_off, tot);
+        vp_buf_emit<OB, ACC>(o_rsrc, g == 0 ? v : -1, row_out, lane_out, pad_off, tot);
     }
     // ---------------------------------------------------------------- small populations: one row group each
     const int n_small = (n8 - n_mid_end + groups - 1) / groups;
@@ -1911,20 +1604,18 @@ __global__ __launch_bounds__(kBlock) void vp_gather_vox_kernel(const VpVoxArgs a
         }
         const int maxlen = vp_group_max(pe - pb, lpr, groups);   // (items at a class border mix two populations)
         float4 acc = zero4;
-        vp_vox_piece<FB, FUSED, VB>(acc, pb, pe, maxlen, cl, ingroup, g, gs, vb, f_rsrc, row_in, lane_in, idw, prw, a);
-        vp_buf_emit<OB, ACC>(o_rsrc, v | kill, row_out, lane_out, pad_off, acc);
+        vp_vox_piece<FB, FUSED>(acc, pb, pe, maxlen, cl, ingroup, g, gs, vb, f_rsrc, row_in, lane_in, idw, prw, a);
+        vp_buf_emit<OB, ACC>(o_rsrc, v, row_out, lane_out, pad_off, acc);
     }
-    if constexpr (VB == 16) {
-        if (pack) {
-            woff = (woff + n_small) % nwaves;
-            const int gw2 = (gw - woff + nwaves) % nwaves;
-            woff = (woff + (n4 - n8 + groups * 2 - 1) / (groups * 2)) % nwaves;
-            const int gw4 = (gw - woff + nwaves) % nwaves;
-            vp_vox_small<FB, OB, ACC, FUSED, VB, 2>(n8, n4, gw2, nwaves, cl, ingroup, g, gs, groups, lpr, f_rsrc, o_rsrc, row_in, lane_in, row_out,
-                                                    lane_out, pad_off, kill, idw, prw, a);
-            vp_vox_small<FB, OB, ACC, FUSED, VB, 4>(n4, nonempty, gw4, nwaves, cl, ingroup, g, gs, groups, lpr, f_rsrc, o_rsrc, row_in, lane_in,
-                                                    row_out, lane_out, pad_off, kill, idw, prw, a);
-        }
+    if (pack) {
+        woff = (woff + n_small) % nwaves;
+        const int gw2 = (gw - woff + nwaves) % nwaves;
+        woff = (woff + (n4 - n8 + groups * 2 - 1) / (groups * 2)) % nwaves;
+        const int gw4 = (gw - woff + nwaves) % nwaves;
+        vp_vox_small<FB, OB, ACC, FUSED, 2>(n8, n4, gw2, nwaves, cl, ingroup, g, gs, groups, lpr, f_rsrc, o_rsrc, row_in, lane_in, row_out,
+                                            lane_out, pad_off, idw, prw, a);
+        vp_vox_small<FB, OB, ACC, FUSED, 4>(n4, nonempty, gw4, nwaves, cl, ingroup, g, gs, groups, lpr, f_rsrc, o_rsrc, row_in, lane_in,
+                                            row_out, lane_out, pad_off, idw, prw, a);
     }
 }
 
@@ -1964,7 +1655,7 @@ struct GatherGeom {
     int w_nom;              // slots between consecutive wave windows (window = groups * ch slots)
 };
 
-GatherGeom gather_geom(long long total_pts, int C) {
+GatherGeom gather_geom(int C) {
     GatherGeom G;
     G.v2 = false; G.lpr = G.groups = G.ch = G.w_nom = 0;
     if (C % 4 == 0 && C / 4 <= 64 && C / 4 >= 6) {
@@ -1972,32 +1663,44 @@ GatherGeom gather_geom(long long total_pts, int C) {
         G.lpr = C / 4;
         G.groups = 64 / G.lpr;
         G.ch = G.lpr - 2 < kChunkMax ? G.lpr - 2 : kChunkMax;
-        static const int ch_env = [] { const char *e = getenv("SGV3D_VP_CH"); return e ? atoi(e) : 0; }();          // (probe knobs)
-        static const int margin_env = [] { const char *e = getenv("SGV3D_VP_MARGIN"); return e ? atoi(e) : -1; }();
-        if (ch_env > 0 && ch_env < G.ch) G.ch = ch_env;
         const int cap = G.groups * G.ch;
         // the margin lets the last owned run finish inside the window (same batch of loads) in most waves
-        int margin = cap / 4 < 8 ? cap / 4 : 8;
-        if (margin_env >= 0 && margin_env < cap) margin = margin_env;
+        const int margin = cap / 4 < 8 ? cap / 4 : 8;
         G.w_nom = cap - margin;
     }
-    (void)total_pts;
     return G;
 }
 
 // workgroups appended to the gather grid for the plan's long runs (idle ones leave after one load)
 constexpr int kLongBlocks = 1024;
 
-// 0: by the rule in launch_gather, 1: slot-balanced kernel, 2: voxel-owner kernel (SGV3D_VP_KERNEL=slot | vox at load time,
-// sgv3d_voxel_pooling_select_kernel at run time: tests and probes run both on the same data)
-std::atomic<int> g_vp_kernel{[] { const char *e = getenv("SGV3D_VP_KERNEL"); return !e ? 0 : e[0] == 's' ? 1 : e[0] == 'v' ? 2 : 0; }()};
+// sgv3d_voxel_pooling_select_kernel: 0 / 2 = the rule of vp_pick_gather, 1 = vp_gather3_kernel wherever the rule would pick the
+// voxel-owner kernel (how tests and probes run the large-tensor kernel on small data)
+std::atomic<int> g_vp_kernel{0};
 
-bool vp_use_vox(long long total_pts, long long V, bool fused) {
-    // One kernel for both forms: the fused lift-splat launch is bitwise lift + operator only if they sum in the same order.
-    // (On sparse grids -- cfg-3 batch 4: 2.8 points per voxel of the grid, nine voxels in ten empty -- the slot-balanced
-    // kernel, which walks the voxels in spatial order, reads the operator's rows with more line reuse: 232 against 270 us.)
-    (void)total_pts; (void)V; (void)fused;
-    return g_vp_kernel.load(std::memory_order_relaxed) != 1;
+// THE selection rule of the planned gather (launch_gather and sgv3d_voxel_pooling_kernel_for both ask here).
+//   kVoxelOwner  vp_gather_vox_kernel: C % 4 == 0, 24 <= C <= 256 and both tensors addressable with 32-bit byte offsets (its
+//                dead slots point past the end of the buffer).  One kernel for the operator and the fused form: the fused
+//                lift-splat launch is bitwise lift + operator only if they sum in the same order.
+//   kSlotWide    vp_gather3_kernel (64-bit addressing): the same channel counts, a feature or output tensor of 4 GB or more.
+//   kPerVoxel    vp_gather_kernel: every other channel count.
+enum class VpGather { kVoxelOwner, kSlotWide, kPerVoxel };
+struct GatherPick {
+    VpGather kernel;
+    unsigned long long fbytes, obytes;      // bytes of the feature (FUSED: context) and the output tensor
+};
+
+// feat_rows: rows of the feature tensor (B * N; FUSED: B * P); feat_elem / out_elem: bytes per element (4, or 2 for bf16);
+// ldo: channels per bf16 output row
+GatherPick vp_pick_gather(const PlanLayout &L, int C, long long feat_rows, int feat_elem, int out_elem, int ldo) {
+    GatherPick p;
+    p.fbytes = (unsigned long long)feat_rows * C * feat_elem;
+    p.obytes = (unsigned long long)L.V * (out_elem == 2 ? ldo * 2 : C * 4);
+    const bool narrow = p.fbytes < 0xfff00000ull && p.obytes < 0xfff00000ull && L.total < 0x7ff00000ll;
+    if (!gather_geom(C).v2) p.kernel = VpGather::kPerVoxel;
+    else if (narrow && g_vp_kernel.load(std::memory_order_relaxed) != 1) p.kernel = VpGather::kVoxelOwner;
+    else p.kernel = VpGather::kSlotWide;
+    return p;
 }
 
 template <bool FUSED, bool FB = false, bool OB = false, bool ACC = false>
@@ -2009,73 +1712,38 @@ int launch_gather(int B, int N, int C, int X, int Y, const void *plan, const flo
     const int *seg = reinterpret_cast<const int *>(base + L.off_seg);
     const int *order = reinterpret_cast<const int *>(base + L.off_order);
     const int *slotvox = reinterpret_cast<const int *>(base + L.off_slotvox);
-    const GatherGeom G = gather_geom(L.total, C);
-    if (G.v2) {
+    const GatherGeom G = gather_geom(C);
+    const GatherPick pick = vp_pick_gather(L, C, FUSED ? (long long)B * P : L.total, FB ? 2 : 4, OB ? 2 : 4, ldo);
+    if (pick.kernel == VpGather::kVoxelOwner) {
+        // Round 4's kernel against the slot-balanced one of round 3 (since removed): fused form 16 / 71 / 140 us against
+        // 21 / 138 / 166 us at cfg-2 / cfg-5 / cfg-3 batch 4, operator form 25.7 / 185 / 270 against 26.7 / 243 / 232 us (on
+        // cfg-3's sparse grid -- 2.8 points per voxel, nine voxels in ten empty -- a walk in spatial order reads the operator's
+        // rows with more line reuse).
+        VpVoxArgs a;
+        a.order = order;
+        a.perm = reinterpret_cast<const int4 *>(base + L.off_perm);
+        a.cls = reinterpret_cast<const int *>(base + L.off_bins) + (size_t)kVoxClasses * L.ncw;
+        a.feats = FUSED ? static_cast<const void *>(ctx) : static_cast<const void *>(feats); a.out = out; a.gate = gate;
+        a.zero_on_gate = zero_on_gate ? 1 : 0;
+        a.prob = prob; a.P = P;
+        a.feat_bytes = (unsigned)pick.fbytes; a.out_bytes = (unsigned)pick.obytes;
+        // workgroups: 1 024 (4 per CU) for frames of up to a million points, 4 096 from two million (cfg-2: 15.3 us fused
+        // with 1 024 against 16.7 / 18.5 with 2 048 / 4 096; cfg-3 batch 4: 238 us operator with 4 096 against 251 / 257;
+        // cfg-5: 178 against 181 / 186)
+        const int vgrid = L.total >= 2000000 ? 4 * kVoxGrid : L.total >= 1000000 ? 2 * kVoxGrid : kVoxGrid;
+        if (FUSED) {
+            const VpMagic mn = vp_magic(N), mp = vp_magic(P);
+            a.magN = mn.mag; a.shN = mn.sh; a.magP = mp.mag; a.shP = mp.sh;
+        }
+        a.V = (int)L.V; a.C = C; a.lpr = G.lpr; a.groups = G.groups; a.vb = G.lpr < kVoxRows ? G.lpr : kVoxRows;
+        a.ldo = ldo; a.N = N;
+        hipLaunchKernelGGL((vp_gather_vox_kernel<FB, OB, ACC, FUSED>), dim3(vgrid), dim3(kBlock), 0, st, a);
+        return check_launch(FUSED ? "vp_gather_vox_kernel (lift-splat)" : "vp_gather_vox_kernel");
+    }
+    if (pick.kernel == VpGather::kSlotWide) {
         const long long waves = (L.total + G.w_nom - 1) / G.w_nom;
         const int nblk = cdiv(waves, kBlock / 64);
         const int nlong = L.long_cap < kLongBlocks ? L.long_cap : kLongBlocks;
-        {
-            // the instruction-lean kernel addresses both tensors with 32-bit byte offsets (dead slots point past the end)
-            const unsigned long long fbytes = (FUSED ? (unsigned long long)B * P : (unsigned long long)L.total) * C * (FB ? 2 : 4);
-            const unsigned long long obytes = (unsigned long long)L.V * (OB ? ldo * 2 : C * 4);
-            static const bool generic_env = [] { const char *e = getenv("SGV3D_VP_GENERIC"); return e && e[0] == '1'; }();
-            // The voxel-owner kernel (round 4) unless sgv3d_voxel_pooling_select_kernel / SGV3D_VP_KERNEL=slot asks for the
-            // slot-balanced one of round 3: fused form 16 / 71 / 140 us against 21 / 138 / 166 us at cfg-2 / cfg-5 / cfg-3
-            // batch 4, operator form 25.7 / 185 / 270 against 26.7 / 243 / 232 us.
-            const bool use_vox = vp_use_vox(L.total, L.V, FUSED);
-            if (fbytes < 0xfff00000ull && obytes < 0xfff00000ull && L.total < 0x7ff00000ll && !generic_env && use_vox) {
-                VpVoxArgs a;
-                a.order = order; a.seg_start = seg;
-                a.perm = reinterpret_cast<const int4 *>(base + L.off_perm);
-                a.cls = reinterpret_cast<const int *>(base + L.off_bins) + (size_t)kVoxClasses * L.ncw;
-                a.feats = FUSED ? static_cast<const void *>(ctx) : static_cast<const void *>(feats); a.out = out; a.gate = gate;
-                a.zero_on_gate = zero_on_gate ? 1 : 0;
-                a.prob = prob; a.P = P;
-                a.feat_bytes = (unsigned)fbytes; a.out_bytes = (unsigned)obytes;
-                // rows in flight per lane: 16 (4 waves per SIMD) or, SGV3D_VP_VB=8, 8 (<= 76 VGPRs: 6-7 waves per SIMD);
-                // SGV3D_VP_GRID: workgroups of the launch (probe knobs, tools/vp_probe3.py)
-                static const int vb_env = [] { const char *e = getenv("SGV3D_VP_VB"); return e ? atoi(e) : 0; }();
-                static const int grid_env = [] { const char *e = getenv("SGV3D_VP_GRID"); return e ? atoi(e) : 0; }();
-                // SGV3D_VP_DEBUG: bits 8 / 16 pick other (equally correct) forms of the zero-row phase / small-voxel packing; bits
-                // 1 / 2 / 4 drop the zero rows / row stores / row loads -- wrong results by design, for tools/vp_probe3.py only, and
-                // honoured only together with SGV3D_VP_DEBUG_WRONG_RESULTS=1
-                static const int dbg_env = [] {
-                    const char *e = getenv("SGV3D_VP_DEBUG"), *w = getenv("SGV3D_VP_DEBUG_WRONG_RESULTS");
-                    const int v = e ? atoi(e) : 0;
-                    return (w && w[0] == '1') ? v : (v & ~7);
-                }();
-                a.dbg = dbg_env;
-                const int VBsel = vb_env == 16 || vb_env == 8 ? vb_env : 16;
-                // workgroups: 1 024 (4 per CU) for frames of up to a million points, 4 096 from two million (cfg-2: 15.3 us fused
-                // with 1 024 against 16.7 / 18.5 with 2 048 / 4 096; cfg-3 batch 4: 238 us operator with 4 096 against 251 / 257;
-                // cfg-5: 178 against 181 / 186)
-                const int vgrid = grid_env > 0 ? grid_env : L.total >= 2000000 ? 4 * kVoxGrid : L.total >= 1000000 ? 2 * kVoxGrid : kVoxGrid;
-                if (FUSED) {
-                    const VpMagic mn = vp_magic(N), mp = vp_magic(P);
-                    a.magN = mn.mag; a.shN = mn.sh; a.magP = mp.mag; a.shP = mp.sh;
-                }
-                a.V = (int)L.V; a.C = C; a.lpr = G.lpr; a.groups = G.groups; a.vb = G.lpr < VBsel ? G.lpr : VBsel;
-                a.ldo = ldo; a.N = N;
-                if (VBsel == 16)
-                    hipLaunchKernelGGL((vp_gather_vox_kernel<FB, OB, ACC, FUSED, 16>), dim3(vgrid), dim3(kBlock), 0, st, a);
-                else
-                    hipLaunchKernelGGL((vp_gather_vox_kernel<FB, OB, ACC, FUSED, 8>), dim3(vgrid), dim3(kBlock), 0, st, a);
-                return check_launch(FUSED ? "vp_gather_vox_kernel (lift-splat)" : "vp_gather_vox_kernel");
-            }
-            if (fbytes < 0xfff00000ull && obytes < 0xfff00000ull && L.total < 0x7ff00000ll && !generic_env) {
-                VpFastArgs a;
-                a.seg_start = seg; a.order = order; a.slot_voxel = slotvox;
-                a.long_list = reinterpret_cast<const int *>(base + L.off_long);
-                a.feats = FUSED ? static_cast<const void *>(ctx) : static_cast<const void *>(feats); a.out = out; a.gate = gate;
-                a.zero_on_gate = zero_on_gate ? 1 : 0;
-                a.prob = prob; a.P = P;
-                a.feat_bytes = (unsigned)fbytes; a.out_bytes = (unsigned)obytes;
-                a.V = (int)L.V; a.C = C; a.lpr = G.lpr; a.groups = G.groups; a.ch = G.ch; a.w_nom = G.w_nom; a.ldo = ldo;
-                a.long_cap = L.long_cap; a.nblk_regular = nblk; a.N = N;
-                hipLaunchKernelGGL((vp_gather_fast_kernel<FB, OB, ACC, FUSED>), dim3(nblk + nlong), dim3(kBlock), 0, st, a);
-                return check_launch(FUSED ? "vp_gather_fast_kernel (lift-splat)" : "vp_gather_fast_kernel");
-            }
-        }
         hipLaunchKernelGGL((vp_gather3_kernel<FUSED, FB, OB, ACC>), dim3(nblk + nlong), dim3(kBlock), 0, st, L.V, C, G.lpr,
                            G.groups, G.ch, G.w_nom, seg, order, slotvox, feats, prob, ctx, N, P, out, ldo,
                            reinterpret_cast<const int *>(base + L.off_long), L.long_cap, nblk, gate, zero_on_gate ? 1 : 0);
@@ -2393,7 +2061,7 @@ int level1_forward(int batch_size, int num_points, int num_channels, int num_vox
     if (int rc = check_common(B, N, C, X, Y, Z)) return rc;
     SGV3D_REQUIRE(geom_xyz && input_features && output_features, "voxel_pooling_forward: null pointer");
     hipStream_t st = as_stream(stream);
-    const GatherGeom G = gather_geom((long long)B * N, C);
+    const GatherGeom G = gather_geom(C);
     const bool aligned = ((reinterpret_cast<uintptr_t>(input_features) | reinterpret_cast<uintptr_t>(output_features)) & 15) == 0;
     std::lock_guard<std::mutex> lock(g_l1_mutex);
     g_l1_stats[0]++;
@@ -2537,13 +2205,16 @@ extern "C" int sgv3d_voxel_pooling_forward_fresh(int batch_size, int num_points,
 extern "C" int sgv3d_voxel_pooling_kernel_for(int batch_size, int num_points, int num_channels, int num_voxel_x, int num_voxel_y,
                                               int fused) {
     if (batch_size <= 0 || num_points <= 0 || num_voxel_x <= 0 || num_voxel_y <= 0) return 0;
-    const GatherGeom G = gather_geom((long long)batch_size * num_points, num_channels);
-    if (!G.v2) return 0;
-    return vp_use_vox((long long)batch_size * num_points, (long long)batch_size * num_voxel_x * num_voxel_y, fused != 0) ? 2 : 1;
+    if ((long long)batch_size * num_points >= 0x7fffffffLL || (long long)batch_size * num_voxel_x * num_voxel_y >= 0x7fffffffLL) return 0;
+    // the f32 forms.  The fused form's context tensor has B * P rows and P is not an argument: P = N (one depth bin), the
+    // largest the point count allows, so the answer never names the voxel-owner kernel for a launch that cannot take it
+    (void)fused;
+    const PlanLayout L = plan_layout(batch_size, num_points, num_voxel_x, num_voxel_y);
+    return vp_pick_gather(L, num_channels, L.total, 4, 4, 0).kernel == VpGather::kVoxelOwner ? 2 : 0;
 }
 
 extern "C" int sgv3d_voxel_pooling_select_kernel(int which) {
-    SGV3D_REQUIRE(which >= 0 && which <= 2, "voxel_pooling_select_kernel: 0 (rule), 1 (slot-balanced) or 2 (voxel-owner)");
+    SGV3D_REQUIRE(which >= 0 && which <= 2, "voxel_pooling_select_kernel: 0 or 2 (the rule), 1 (vp_gather3_kernel in place of the voxel-owner kernel)");
     g_vp_kernel.store(which, std::memory_order_relaxed);
     return SGV3D_OK;
 }

@@ -11,12 +11,13 @@ DEV = "cuda:0"
 VP_CASES = ["tiny", "b2_c80", "z2", "dups", "all_out"]
 
 
-@pytest.fixture(params=["rule", "slot", "vox"])
+@pytest.fixture(params=[pytest.param("default", id="rule"), "slot"])   # (id "rule": the cases keep their names)
 def gather_kernel(request, hip):
-    """Both gather kernels on the same data: the slot-balanced one of round 3 and the voxel-owner one of round 4 (the default
-    picks per form and grid density, csrc/voxel_pooling.hip::launch_gather)."""
+    """Both planned gathers for 24 <= C <= 256 on the same data: ``default`` is the library's rule (the voxel-owner kernel at
+    these sizes), ``slot`` forces vp_gather3_kernel, the slot-balanced kernel with 64-bit addressing that the rule keeps for
+    tensors of 4 GB or more (csrc/voxel_pooling.hip::vp_pick_gather)."""
     lib = hip.load()
-    hip.check(lib.sgv3d_voxel_pooling_select_kernel({"rule": 0, "slot": 1, "vox": 2}[request.param]), "select")
+    hip.check(lib.sgv3d_voxel_pooling_select_kernel({"default": 0, "slot": 1}[request.param]), "select")
     yield request.param
     hip.check(lib.sgv3d_voxel_pooling_select_kernel(0), "select")
 
@@ -384,7 +385,7 @@ def test_random_geometry_fuzz_vs_oracle(hip, seed, gather_kernel):
 @pytest.mark.parametrize("C", [80, 64, 24, 88, 256])
 def test_gather_runs_cut_by_chunk_and_wave_borders(hip, C, gather_kernel):
     """vp_gather3_kernel: voxel populations chosen around every border of its decomposition -- one chunk (<= 16 slots), one
-    wave range (groups x ch slots: 48 at C=80, 56 at C=64, 40 at C=24, 32 at C=88, 16 at C=256), kLongRun = 256 (longer runs
+    wave range (groups x ch slots: 48 at C=80, 56 at C=64, 40 at C=24, 32 at C=88, 16 at C=256), kLongRun = 128 (longer runs
     go to the long-run workgroups), several ranges, and thousands of points -- in shuffled point order, two samples, empty
     voxels between them.  Integer-valued features: exact against the oracle; output fully written (NaN-prefilled)."""
     lens = [1, 2, 15, 16, 17, 31, 32, 33, 39, 40, 41, 47, 48, 49, 55, 56, 57, 95, 96, 97, 255, 256, 257, 258, 300, 511, 513,

@@ -2,7 +2,7 @@
 """Dev probe: the planned gather (operator form and fused lift-splat form) on the cfg-2 and cfg-5 geometries, timed as a
 hipGraph of 20 launches (GPU time, not the host's launch cadence).  Run once per kernel:
     python tools/vp_probe3.py                       # voxel-owner kernel (vp_gather_vox_kernel, default)
-    SGV3D_VP_KERNEL=slot python tools/vp_probe3.py  # slot-balanced kernel of round 3
+    SGV3D_VP_KERNEL=slot python tools/vp_probe3.py  # vp_gather3_kernel, the large-tensor kernel, at these sizes
 Also checks the fused form against lift + operator bit for bit, and the level-1 entry's time per call."""
 import os
 import sys
@@ -42,6 +42,8 @@ def graph_us(fn, reps=20):
 
 def main():
     kern = os.environ.get("SGV3D_VP_KERNEL", "vox")
+    rc = _lib.load().sgv3d_voxel_pooling_select_kernel(1 if kern.startswith("s") else 0)
+    assert rc == 0, rc
     for name, conf, batch in (("cfg2", S.r50_256_conf, 1), ("cfg5", S.bsm_r101_256_conf, 1), ("cfg3_b4", S.r101_512_conf, 4)):
         bc, hc = conf()
         torch.manual_seed(0)
