@@ -874,6 +874,18 @@ size_t sgv3d_conv2d_backward_weight_bf16_batched_workspace_bytes(const sgv3d_con
 int sgv3d_conv2d_backward_weight_bf16_batched(const sgv3d_conv_desc *desc /*host*/, const float *x, const float *const *dy_list /*host*/,
                                               float *const *dw_list /*host*/, int n, int split, void *workspace,
                                               size_t workspace_bytes, void *stream);
+/* The two single-layer forms (sgv3d_conv2d_backward_weight_bf16, ..._alltaps) reading bf16 TENSORS -- bf16 activation storage in training (hip_ops.TRAIN_BF16_STORAGE): x and dy
+ * are bf16 NHWC as the image backbone keeps them in HBM, dw stays f32.  Only the staging differs (8-byte loads of 4 channels, stored
+ * into the LDS image without conversion); tiles, split, workspace layout and the fixed-order reduce are the same, so for one
+ * (desc.tile, split) the result is BITWISE that of the f32-tensor entry fed the upcast values.  Channel strides and offsets % 8 == 0
+ * (the layout contract of the bf16 maps: whole 16-byte units per pixel, as the BatchNorm and convolution kernels on them need; the
+ * 8-byte loads here would take multiples of 4), channel counts % 4 == 0, x / dy 16-byte aligned. */
+size_t sgv3d_conv2d_backward_weight_bf16_tensors_workspace_bytes(const sgv3d_conv_desc *desc /*host*/, int split);
+int sgv3d_conv2d_backward_weight_bf16_tensors(const sgv3d_conv_desc *desc /*host*/, const void *x, const void *dy, float *dw, int split,
+                                              void *workspace, size_t workspace_bytes, void *stream);
+size_t sgv3d_conv2d_backward_weight_bf16_alltaps_tensors_workspace_bytes(const sgv3d_conv_desc *desc /*host*/, int split);
+int sgv3d_conv2d_backward_weight_bf16_alltaps_tensors(const sgv3d_conv_desc *desc /*host*/, const void *x, const void *dy, float *dw,
+                                                      int split, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Batched form of the all-taps kernel (desc.tile 5 layers: 3x3 / stride 1 / dilation 1): n <= 48 weight gradients
  * dw_list[i] = wgrad(x, dy_list[i]) of layers that read the SAME input, in one launch (blockIdx.z = problem).  The 36 first layers of
@@ -987,6 +999,25 @@ int sgv3d_batchnorm_train_backward(long long pixels, int channels, const float *
 int sgv3d_batchnorm_relu_train_backward_from_x(long long pixels, int channels, const float *x, const float *dy, const float *gamma,
                                                const float *beta, const float *save_mean, const float *save_invstd, float *dx,
                                                float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The three BatchNorm entries on bf16 NHWC maps (bf16 activation storage in training): x, residual, y, dy, dx, dresidual are bf16;
+ * gamma, beta, the saved and running statistics, dgamma and dbeta stay f32, the per-range partials float64 (the workspace, the finalize
+ * kernels and their roundings are those of the f32 entries).  The arithmetic is the f32 kernels' on the upcast values --
+ * fmaf(x, scale, shift) (+ residual), max -- followed by one round-to-nearest-even to bf16; the statistics are those of the stored
+ * (rounded) x; the from-x ReLU mask is fmaf(x, scale, shift) > 0 in f32.  channels % 8 == 0 (a 16-byte load is 8 channels) and 16-byte
+ * aligned buffers, else SGV3D_EINVAL before any launch.  No atomics, fixed summation order. */
+int sgv3d_batchnorm_train_forward_bf16(long long pixels, int channels, const void *x, const void *residual, const float *gamma,
+                                       const float *beta, float *running_mean, float *running_var, float momentum, float eps,
+                                       int relu, void *y, float *save_mean, float *save_invstd, void *workspace,
+                                       size_t workspace_bytes, void *stream);
+int sgv3d_batchnorm_train_backward_bf16(long long pixels, int channels, const void *x, const void *y, const void *dy,
+                                        const float *gamma, const float *save_mean, const float *save_invstd, int relu, void *dx,
+                                        void *dresidual, float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                                        void *stream);
+int sgv3d_batchnorm_relu_train_backward_from_x_bf16(long long pixels, int channels, const void *x, const void *dy, const float *gamma,
+                                                    const float *beta, const float *save_mean, const float *save_invstd, void *dx,
+                                                    float *dgamma, float *dbeta, void *workspace, size_t workspace_bytes,
+                                                    void *stream);
 
 /* y[b, 2 i + py, 2 j + px, :] = phases[py * 2 + px][b, i + row0, j + col0, :]: interleaves the four sub-pixel phases of a
  * stride-2 data gradient (each phase is a stride-1 convolution of the upstream gradient with the taps of its parity,

@@ -157,6 +157,10 @@ _PROTOS = {
     "sgv3d_conv2d_backward_weight_bf16_batched": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "sgv3d_conv2d_backward_weight_bf16_alltaps_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvDesc), c_int, c_int]),
     "sgv3d_conv2d_backward_weight_bf16_alltaps": (c_int, [ctypes.POINTER(ConvDesc)] + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_void_p]),
+    "sgv3d_conv2d_backward_weight_bf16_tensors_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvDesc), c_int]),
+    "sgv3d_conv2d_backward_weight_bf16_tensors": (c_int, [ctypes.POINTER(ConvDesc)] + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_void_p]),
+    "sgv3d_conv2d_backward_weight_bf16_alltaps_tensors_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvDesc), c_int]),
+    "sgv3d_conv2d_backward_weight_bf16_alltaps_tensors": (c_int, [ctypes.POINTER(ConvDesc)] + [c_void_p] * 3 + [c_int, c_void_p, c_size_t, c_void_p]),
     "sgv3d_conv2d_backward_weight_bf16_alltaps_batched": (c_int, [ctypes.POINTER(ConvDesc), c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "sgv3d_conv2d_backward_weight_thin_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvDesc)]),
     "sgv3d_conv2d_backward_weight_batched_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvDesc), c_int, c_int]),
@@ -177,6 +181,10 @@ _PROTOS = {
                                       [c_void_p] * 4 + [c_size_t, c_void_p]),
     "sgv3d_batchnorm_relu_train_backward_from_x": (c_int, [c_ll, c_int] + [c_void_p] * 9 + [c_void_p, c_size_t, c_void_p]),
     "sgv3d_batchnorm_train_backward": (c_int, [c_ll, c_int] + [c_void_p] * 6 + [c_int] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "sgv3d_batchnorm_train_forward_bf16": (c_int, [c_ll, c_int] + [c_void_p] * 6 + [ctypes.c_float, ctypes.c_float, c_int] +
+                                           [c_void_p] * 4 + [c_size_t, c_void_p]),
+    "sgv3d_batchnorm_relu_train_backward_from_x_bf16": (c_int, [c_ll, c_int] + [c_void_p] * 9 + [c_void_p, c_size_t, c_void_p]),
+    "sgv3d_batchnorm_train_backward_bf16": (c_int, [c_ll, c_int] + [c_void_p] * 6 + [c_int] + [c_void_p] * 5 + [c_size_t, c_void_p]),
     "sgv3d_adamw_step": (c_int, [c_ll] + [c_void_p] * 4 + [c_int] + [ctypes.c_float] * 6 + [c_void_p] * 2),
     "sgv3d_adamw_step_dev": (c_int, [c_ll] + [c_void_p] * 5 + [ctypes.c_float] * 5 + [c_void_p] * 2),
     "sgv3d_adamw_set_hyper": (c_int, [c_void_p, c_int] + [ctypes.c_float] * 3 + [c_void_p]),

@@ -41,6 +41,10 @@ def conv2d_backward_weight(x, dy, kernel, stride=1, pad=0, dil=1, *, cin=None, c
     _, OH, OW, y_ld = (int(v) for v in dy.shape)
     cin = x_ld - x_coff if cin is None else int(cin)
     cout = y_ld - y_coff if cout is None else int(cout)
+    if x.dtype == torch.bfloat16:
+        # bf16 activation storage: only the bf16-MFMA kernels read bf16 tensors (no other kernel does: a layer they do not take raises)
+        return conv2d_backward_weight_bf16(x, dy, (kh, kw), stride, pad, dil, cin=cin, cout=cout, x_coff=x_coff, y_coff=y_coff, split=split,
+                                           tile=tile, out=out)
     assert x.is_contiguous() and dy.is_contiguous() and x.dtype == dy.dtype == torch.float32 and x.is_cuda
     assert (OH, OW) == _out_hw(H, W, (kh, kw), stride, pad, dil) and int(dy.shape[0]) == B
     d = ConvDesc()
@@ -80,6 +84,8 @@ def conv2d_backward_weight(x, dy, kernel, stride=1, pad=0, dil=1, *, cin=None, c
 
 def _bf16_wgrad_ok(x, dy, cin, cout, x_coff, y_coff):
     x_ld, y_ld = int(x.shape[-1]), int(dy.shape[-1])
+    if x.dtype == torch.bfloat16 and (x_ld % 8 or y_ld % 8 or x_coff % 8 or y_coff % 8):      # bf16 tensors: 16-byte pixel rows
+        return False
     return (cin % 4 == 0 and cout % 4 == 0 and x_ld % 4 == 0 and y_ld % 4 == 0 and x_coff % 4 == 0 and y_coff % 4 == 0
             and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0 and min(cin, cout) >= 16)
 
@@ -89,18 +95,23 @@ def conv2d_backward_weight_bf16(x, dy, kernel, stride=1, pad=0, dil=1, *, cin=No
     and out, operands rounded to bf16 while staging, f32 accumulation, fixed-order pixel-split reduce.  ``tile``: 0 = measured per
     layer shape (first call) / the library's rule, 1 = 64 x 64, 4 = 128 x 128 (one tap per workgroup, ``split`` = pixel ranges), 6 = the
     all-taps kernel (3x3 / stride 1: a workgroup owns a 64 x 64 tile for all nine taps and walks down a column of the map;
-    ``split`` = row chunks per column, 0 = rule)."""
+    ``split`` = row chunks per column, 0 = rule).
+    bfloat16 ``x`` and ``dy`` (bf16 activation storage): the ``*_tensors`` entries -- the same kernels with a staging that moves the
+    stored bf16 values; for one (tile, split) bitwise the f32-tensor result on the upcast values.  Channel strides / offsets % 8."""
     from . import hip_ops
+    t16 = x.dtype == torch.bfloat16
+    sfx = "_tensors" if t16 else ""
+    esz = 2.0 if t16 else 4.0
     kh, kw = (kernel, kernel) if isinstance(kernel, int) else kernel
     B, H, W, x_ld = (int(v) for v in x.shape)
     _, OH, OW, y_ld = (int(v) for v in dy.shape)
     cin = x_ld - x_coff if cin is None else int(cin)
     cout = y_ld - y_coff if cout is None else int(cout)
-    assert x.is_contiguous() and dy.is_contiguous() and x.dtype == dy.dtype == torch.float32 and x.is_cuda
+    assert x.is_contiguous() and dy.is_contiguous() and x.dtype == dy.dtype and x.dtype in (torch.float32, torch.bfloat16) and x.is_cuda
     assert (OH, OW) == _out_hw(H, W, (kh, kw), stride, pad, dil) and int(dy.shape[0]) == B
     if not _bf16_wgrad_ok(x, dy, cin, cout, x_coff, y_coff):
         raise _lib.SGV3DError("the bf16 weight-gradient kernel needs channel counts, strides and offsets that are multiples of 4 "
-                              "(at least 16 channels on both sides) and 16-byte aligned tensors")
+                              "(of 8 for the strides and offsets of bf16 tensors; at least 16 channels on both sides) and 16-byte aligned tensors")
     d = ConvDesc()
     d.batch, d.in_h, d.in_w, d.cin, d.out_h, d.out_w, d.cout = B, H, W, cin, OH, OW, cout
     d.kh, d.kw, d.stride, d.pad, d.dil = kh, kw, int(stride), int(pad), int(dil)
@@ -112,29 +123,30 @@ def conv2d_backward_weight_bf16(x, dy, kernel, stride=1, pad=0, dil=1, *, cin=No
         d.tile = int(tile)
     if int(tile) == 6:              # all nine taps per workgroup (csrc/conv_wgrad3x3_bf16.hip); split = row chunks per column
         d.tile = 0
-        nws = lib.sgv3d_conv2d_backward_weight_bf16_alltaps_workspace_bytes(ctypes.byref(d), 1, int(split))
+        nws = (lib.sgv3d_conv2d_backward_weight_bf16_alltaps_tensors_workspace_bytes(ctypes.byref(d), int(split)) if t16 else
+               lib.sgv3d_conv2d_backward_weight_bf16_alltaps_workspace_bytes(ctypes.byref(d), 1, int(split)))
         if nws == 0:
             raise _lib.SGV3DError("the all-taps bf16 weight-gradient kernel takes 3x3 / stride-1 layers (dilation <= 20) only")
         ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
         dw = _dw_buffer(out, (cout, cin, kh, kw), x.device)
-        name = "conv_wgrad_bf16_alltaps"
+        name = "conv_wgrad_bf16_alltaps" + sfx
         if hip_ops.PROFILE_DETAIL:
             name += f"|{B}x{H}x{W}x{cin}->{cout} k{kh} s{stride} d{dil} tile6 split{int(split)}"
-        with torch.cuda.device(x.device), prof(name, 2.0 * B * OH * OW * cout * cin * kh * kw, 4.0 * (B * H * W * cin + B * OH * OW * cout + cout * cin * kh * kw)):
-            rc = lib.sgv3d_conv2d_backward_weight_bf16_alltaps(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), int(split),
-                                                               ws.data_ptr(), nws, _st(x))
-        _lib.check(rc, "sgv3d_conv2d_backward_weight_bf16_alltaps")
+        with torch.cuda.device(x.device), prof(name, 2.0 * B * OH * OW * cout * cin * kh * kw, esz * (B * H * W * cin + B * OH * OW * cout) + 4.0 * cout * cin * kh * kw):
+            rc = getattr(lib, "sgv3d_conv2d_backward_weight_bf16_alltaps" + sfx)(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), int(split),
+                                                                                 ws.data_ptr(), nws, _st(x))
+        _lib.check(rc, "sgv3d_conv2d_backward_weight_bf16_alltaps" + sfx)
         return dw
-    nws = lib.sgv3d_conv2d_backward_weight_bf16_workspace_bytes(ctypes.byref(d), int(split))
+    nws = getattr(lib, "sgv3d_conv2d_backward_weight_bf16" + sfx + "_workspace_bytes")(ctypes.byref(d), int(split))
     ws = torch.empty(max(nws, 1), dtype=torch.uint8, device=x.device)
     dw = _dw_buffer(out, (cout, cin, kh, kw), x.device)
-    name = "conv_wgrad_bf16"
+    name = "conv_wgrad_bf16" + sfx
     if hip_ops.PROFILE_DETAIL:
         name += f"|{B}x{H}x{W}x{cin}->{cout} k{kh} s{stride} d{dil} tile{int(tile)} split{int(split)}"
-    with torch.cuda.device(x.device), prof(name, 2.0 * B * OH * OW * cout * cin * kh * kw, 4.0 * (B * H * W * cin + B * OH * OW * cout + cout * cin * kh * kw)):
-        rc = lib.sgv3d_conv2d_backward_weight_bf16(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), int(split),
-                                                   ws.data_ptr(), nws, _st(x))
-    _lib.check(rc, "sgv3d_conv2d_backward_weight_bf16")
+    with torch.cuda.device(x.device), prof(name, 2.0 * B * OH * OW * cout * cin * kh * kw, esz * (B * H * W * cin + B * OH * OW * cout) + 4.0 * cout * cin * kh * kw):
+        rc = getattr(lib, "sgv3d_conv2d_backward_weight_bf16" + sfx)(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), int(split),
+                                                                     ws.data_ptr(), nws, _st(x))
+    _lib.check(rc, "sgv3d_conv2d_backward_weight_bf16" + sfx)
     return dw
 
 
@@ -204,12 +216,20 @@ def _wgrad_choice(lib, d, x, dy, bf16=False):
     sums each tile's pixel ranges in a fixed order, so results differ only by the association of that sum.  ``bf16``: the
     bf16-MFMA kernel (tiles 1 = 64 x 64 and 4 = 128 x 128 only)."""
     from . import hip_ops
-    key = (d.batch, d.in_h, d.in_w, d.cin, d.out_h, d.out_w, d.cout, d.kh, d.kw, d.stride, d.pad, d.dil, d.x_ld, d.y_ld) + (("bf16",) if bf16 else ())
+    t16 = x.dtype == torch.bfloat16        # bf16 tensors (the *_tensors entries of the bf16 kernels): choices of their own
+    key = (d.batch, d.in_h, d.in_w, d.cin, d.out_h, d.out_w, d.cout, d.kh, d.kw, d.stride, d.pad, d.dil, d.x_ld, d.y_ld) + (("bf16",) if bf16 else ()) + (("t16",) if t16 else ())
     if key in _WGRAD_DB:
         return _WGRAD_DB[key]
     sig = "wgrad|" + "x".join(str(v) for v in key)      # committed choices (tune/gfx950_*train*.json): no first-call timing, same kernels every run
     ws_bytes = lib.sgv3d_conv2d_backward_weight_bf16_workspace_bytes if bf16 else lib.sgv3d_conv2d_backward_weight_workspace_bytes
     launch = lib.sgv3d_conv2d_backward_weight_bf16 if bf16 else lib.sgv3d_conv2d_backward_weight
+    alltaps_ws = lambda sp: lib.sgv3d_conv2d_backward_weight_bf16_alltaps_workspace_bytes(ctypes.byref(d), 1, sp)
+    alltaps = lib.sgv3d_conv2d_backward_weight_bf16_alltaps
+    if t16:
+        assert bf16
+        ws_bytes, launch = lib.sgv3d_conv2d_backward_weight_bf16_tensors_workspace_bytes, lib.sgv3d_conv2d_backward_weight_bf16_tensors
+        alltaps_ws = lambda sp: lib.sgv3d_conv2d_backward_weight_bf16_alltaps_tensors_workspace_bytes(ctypes.byref(d), sp)
+        alltaps = lib.sgv3d_conv2d_backward_weight_bf16_alltaps_tensors
     if not hip_ops.AUTOTUNE:
         return 0, 0                                          # the library's own rule, whatever a tune DB holds
     if sig in hip_ops.TUNE_DB and not (sig in hip_ops._COMMITTED_SIGS and not hip_ops._is_gfx950(x.device)):
@@ -247,12 +267,11 @@ def _wgrad_choice(lib, d, x, dy, bf16=False):
             d.tile = t
             if t == 6:
                 d.tile = 0
-                nws = lib.sgv3d_conv2d_backward_weight_bf16_alltaps_workspace_bytes(ctypes.byref(d), 1, sp)
+                nws = alltaps_ws(sp)
                 if nws == 0 or nws > (2 << 30):
                     continue
                 ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
-                run = lambda: lib.sgv3d_conv2d_backward_weight_bf16_alltaps(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), sp,
-                                                                            ws.data_ptr(), nws, _st(x))
+                run = lambda: alltaps(ctypes.byref(d), x.data_ptr(), dy.data_ptr(), dw.data_ptr(), sp, ws.data_ptr(), nws, _st(x))
             else:
                 nws = ws_bytes(ctypes.byref(d), sp)
                 if nws > (2 << 30):
@@ -281,8 +300,13 @@ def _wgrad_choice(lib, d, x, dy, bf16=False):
 def zero_insert(x, stride, out_hw):
     """NHWC map with ``x`` on every ``stride``-th pixel and zeros elsewhere."""
     B, H, W, C = (int(v) for v in x.shape)
-    assert x.is_contiguous() and x.dtype == torch.float32 and C % 4 == 0
-    y = torch.empty(B, out_hw[0], out_hw[1], C, dtype=torch.float32, device=x.device)
+    assert x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16)
+    y = torch.empty(B, out_hw[0], out_hw[1], C, dtype=x.dtype, device=x.device)
+    if x.dtype == torch.bfloat16:
+        # the kernel only moves 16-byte units: a bf16 map with C % 8 == 0 is a float map with C / 2 channels to it -- no new kernel
+        assert C % 8 == 0
+        C //= 2
+    assert C % 4 == 0
     with torch.cuda.device(x.device), prof("zero_insert"):
         rc = _lib.load().sgv3d_zero_insert(B, H, W, C, int(stride), int(out_hw[0]), int(out_hw[1]), x.data_ptr(),
                                            y.data_ptr(), _st(x))
@@ -315,6 +339,12 @@ def conv2d_backward_data(dy, weight, in_hw, stride=1, pad=0, dil=1, add_to=None)
     cout, cin, kh, kw = (int(v) for v in weight.shape)
     H, W = in_hw
     assert kh == kw, "square kernels only (every layer of the model)"
+    if dy.dtype == torch.bfloat16:
+        # bf16 activation storage: the gradient maps stay bf16 (PackedConv's io bits); 16-byte pixel rows on both sides
+        assert cin % 8 == 0 and int(dy.shape[-1]) % 8 == 0 and not (kh == stride and stride > 1), "bf16 data gradient: channel counts % 8, no patchify layers"
+        okw = dict(out_dtype=torch.bfloat16)
+    else:
+        okw = {}
     if int(dy.shape[-1]) % 4:
         dy = torch.nn.functional.pad(dy, (0, 4 - int(dy.shape[-1]) % 4))
     if kh == stride and stride > 1 and pad == 0 and dil == 1:
@@ -327,7 +357,7 @@ def conv2d_backward_data(dy, weight, in_hw, stride=1, pad=0, dil=1, add_to=None)
     cp, rpad = int(dy.shape[-1]), dil * (kh - 1) - pad
     # the stride-1 convolution with the weights rotated by 180 degrees and in / out swapped ([cin, cout, kh, kw])
     make = lambda w: PackedConv(_rot180_transpose(w), stride=1, pad=rpad, dil=dil, cin_pad=cp, pad_out=True)
-    conv = lambda x, **kw: _packed_call(weight, ('dgrad', rpad, dil, cp), make, x, **kw)
+    conv = lambda x, **kw: _packed_call(weight, ('dgrad', rpad, dil, cp), make, x, **okw, **kw)
     if stride == 1:
         return conv(dy, residual=add_to)
     assert add_to is None, "add_to: stride-1 layers only"
@@ -356,13 +386,16 @@ def _dgrad_stride2(dy, weight, in_hw, pad):
     cout, cin, kh, kw = (int(v) for v in weight.shape)
     H, W = in_hw
     B, hc, wc, _ = (int(v) for v in dy.shape)
+    t16 = dy.dtype == torch.bfloat16                       # bf16 activation storage: bf16 phases, bf16 result
+    okw = dict(out_dtype=torch.bfloat16) if t16 else {}
+    assert not t16 or cin % 8 == 0
     outs, geo = [], []
     for py in range(2):
         ty, p_y, n_y = _phase_1d(kh, pad, py, hc, H)
         for px in range(2):
             tx, p_x, n_x = _phase_1d(kw, pad, px, wc, W)
             if not ty or not tx or n_y == 0 or n_x == 0:          # no tap has this parity: the phase is zero
-                outs.append(torch.zeros(B, max(n_y, 1), max(n_x, 1), (cin + 3) // 4 * 4, dtype=torch.float32, device=dy.device))
+                outs.append(torch.zeros(B, max(n_y, 1), max(n_x, 1), (cin + 3) // 4 * 4, dtype=dy.dtype, device=dy.device))
                 geo.append((max(n_y, 1), max(n_x, 1), 0, 0))
                 continue
             # (taps are min, min + 2, ... in descending order: a strided slice and a flip -- indexing with the Python lists would build
@@ -374,11 +407,13 @@ def _dgrad_stride2(dy, weight, in_hw, pad):
             # sub-kernel [cin, cout, Ty, Tx] of the phase
             make = lambda v, ay=ay, ax=ax, pp=pp: PackedConv(v[:, :, ay::2, ax::2].flip(2, 3).transpose(0, 1).contiguous(), stride=1, pad=pp,
                                                              cin_pad=cp, pad_out=True)
-            o = _packed_call(weight, ('dgrad_s2', py, px, pad, pp, cp), make, dy)
+            o = _packed_call(weight, ('dgrad_s2', py, px, pad, pp, cp), make, dy, **okw)
             outs.append(o)
             geo.append((int(o.shape[1]), int(o.shape[2]), pp - p_y, pp - p_x))
     C = int(outs[0].shape[-1])
-    dx = torch.empty(B, H, W, C, dtype=torch.float32, device=dy.device)
+    dx = torch.empty(B, H, W, C, dtype=dy.dtype, device=dy.device)
+    if t16:
+        C //= 2             # the interleave only moves 16-byte units: bf16 maps with C % 8 == 0 as float maps with C / 2 channels -- no new kernel
     ptrs = (ctypes.c_void_p * 4)(*[o.data_ptr() for o in outs])
     arr = lambda i: (ctypes.c_int32 * 4)(*[g[i] for g in geo])
     with torch.cuda.device(dy.device), prof("interleave_phases"):
@@ -398,14 +433,21 @@ class _Conv2dNHWC(torch.autograd.Function):
         cp = int(x.shape[-1])
         ctx.save_for_backward(x, weight)
         ctx.geom = (stride, pad, dil, bias is not None)
+        okw = {}
+        if x.dtype == torch.bfloat16:
+            # bf16 activation storage (the image backbone's stages): a bf16 map in, a bf16 map out -- one rounding after the f32 epilogue
+            assert bias is None, "bf16 tensors: the backbone's convolutions have no bias"
+            assert int(weight.shape[0]) % 8 == 0 and cp % 8 == 0, "bf16 tensors: channel counts % 8"
+            okw = dict(out_dtype=torch.bfloat16)
         return _packed_call(weight, ('fwd', stride, pad, dil, cp, None if bias is None else bias.data_ptr()),
-                            lambda w: PackedConv(w, stride=stride, pad=pad, dil=dil, shift=bias, cin_pad=cp), x)
+                            lambda w: PackedConv(w, stride=stride, pad=pad, dil=dil, shift=bias, cin_pad=cp), x, **okw)
 
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors
         stride, pad, dil, has_bias = ctx.geom
         dy = dy.contiguous()
+        assert dy.dtype == x.dtype                  # (bf16 storage: bf16 dy -> bf16 dx, f32 dw through the bf16-tensor weight gradient)
         cout, cin, kh, kw = (int(v) for v in weight.shape)
         dx = dw = db = None
         if ctx.needs_input_grad[0]:

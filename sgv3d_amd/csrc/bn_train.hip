@@ -363,3 +363,295 @@ int bn_backward(long long pixels, int channels, const float *x, const float *y, 
     return check_launch("bn_bwd_apply_kernel");
 }
 }  // namespace
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The same three entries on bf16 NHWC tensors (mixed-precision training with bf16 activation storage, hip_ops.TRAIN_BF16_STORAGE):
+// x, residual, y, dy, dx, d_residual are bf16, everything per channel stays f32 and the per-range partials float64.  The arithmetic
+// is the f32 kernels' on the upcast values (an upcast is exact), followed by ONE round-to-nearest-even where a map is written; the
+// workspace, the plan, the finalize kernels and their roundings are the ones above.  The passes move half the bytes, which is all
+// that can make an HBM-bound stream faster.
+//
+// Thread layout: one 16-byte load is 8 channels; 8 lanes cover 64 channels of a pixel (128 contiguous bytes), 32 pixel rows per
+// block pass; a block owns the same (64-channel, pixel-range) slab as above, so the partial layout is unchanged.  channels % 8 == 0.
+namespace {
+
+typedef __bf16 bn_bf16x8 __attribute__((ext_vector_type(8)));
+typedef float bn_f32x8 __attribute__((ext_vector_type(8)));
+
+struct BnMaps16 {                          // the bf16 maps of a call (BnArgs carries the f32 / f64 side)
+    const unsigned short *x, *res, *y_in, *dy;
+    unsigned short *y, *dx, *dres;
+};
+
+__device__ __forceinline__ bn_f32x8 up8(const uint4 w) {
+    bn_f32x8 v;
+    v[0] = __uint_as_float(w.x << 16); v[1] = __uint_as_float(w.x & 0xffff0000u);
+    v[2] = __uint_as_float(w.y << 16); v[3] = __uint_as_float(w.y & 0xffff0000u);
+    v[4] = __uint_as_float(w.z << 16); v[5] = __uint_as_float(w.z & 0xffff0000u);
+    v[6] = __uint_as_float(w.w << 16); v[7] = __uint_as_float(w.w & 0xffff0000u);
+    return v;
+}
+
+__device__ __forceinline__ uint4 down8(const bn_f32x8 v) {      // round to nearest even
+    return __builtin_bit_cast(uint4, __builtin_convertvector(v, bn_bf16x8));
+}
+
+__device__ __forceinline__ bn_f32x8 ld8f(const float *p) {
+    const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
+    bn_f32x8 v = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    return v;
+}
+
+// scale / shift of channels c .. c + 7 exactly as bn_finalize_kernel folded them (fold_affine on both halves)
+__device__ __forceinline__ void fold_affine8(const BnArgs &a, int c, const bn_f32x8 mean, const bn_f32x8 istd, bn_f32x8 &sc, bn_f32x8 &sh) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        float4 s4, h4;
+        fold_affine(a, c + 4 * h, make_float4(mean[4 * h], mean[4 * h + 1], mean[4 * h + 2], mean[4 * h + 3]),
+                    make_float4(istd[4 * h], istd[4 * h + 1], istd[4 * h + 2], istd[4 * h + 3]), s4, h4);
+        sc[4 * h] = s4.x; sc[4 * h + 1] = s4.y; sc[4 * h + 2] = s4.z; sc[4 * h + 3] = s4.w;
+        sh[4 * h] = h4.x; sh[4 * h + 1] = h4.y; sh[4 * h + 2] = h4.z; sh[4 * h + 3] = h4.w;
+    }
+}
+
+// the 32 row sums of a block's 64 channels, added in row order, to the partials of this pixel range
+__device__ __forceinline__ void block_partials16(const BnArgs &a, double (*lds)[64][2], int cg, int c8, int prow, const double *s, const double *q) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { lds[prow][c8 + i][0] = s[i]; lds[prow][c8 + i][1] = q[i]; }
+    __syncthreads();
+    if (threadIdx.x < 128) {
+        const int c = threadIdx.x >> 1, k = threadIdx.x & 1;
+        double t = 0;
+        for (int r = 0; r < 32; ++r) t += lds[r][c][k];
+        if (cg + c < a.channels) a.partial[((size_t)blockIdx.y * a.channels + cg + c) * 2 + k] = t;
+    }
+}
+
+__global__ __launch_bounds__(256) void bn_stats_bf16_kernel(const BnArgs a, const BnMaps16 t) {
+    __shared__ double lds[32][64][2];
+    const int cg = blockIdx.x * 64, c8 = (threadIdx.x & 7) * 8, prow = threadIdx.x >> 3;
+    const long long p0 = (long long)blockIdx.y * a.pix_per_range;
+    const long long p1 = p0 + a.pix_per_range < a.pixels ? p0 + a.pix_per_range : a.pixels;
+    double s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (cg + c8 < a.channels) {
+        const unsigned short *base = t.x + cg + c8;
+        long long p = p0 + prow;
+        for (; p + 96 < p1; p += 128) {          // four loads in flight per thread
+            uint4 w[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) w[u] = *reinterpret_cast<const uint4 *>(base + (p + 32 * u) * a.channels);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const bn_f32x8 v = up8(w[u]);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) { s[i] += v[i]; q[i] += (double)v[i] * v[i]; }
+            }
+        }
+        for (; p < p1; p += 32) {
+            const bn_f32x8 v = up8(*reinterpret_cast<const uint4 *>(base + p * a.channels));
+#pragma unroll
+            for (int i = 0; i < 8; ++i) { s[i] += v[i]; q[i] += (double)v[i] * v[i]; }
+        }
+    }
+    block_partials16(a, lds, cg, c8, prow, s, q);
+}
+
+__global__ __launch_bounds__(256) void bn_apply_bf16_kernel(const BnArgs a, const BnMaps16 t) {
+    const int c8n = a.channels / 8;
+    const long long total = a.pixels * c8n;
+    const uint4 *x8 = reinterpret_cast<const uint4 *>(t.x), *r8 = reinterpret_cast<const uint4 *>(t.res);
+    uint4 *y8 = reinterpret_cast<uint4 *>(t.y);
+    const float floor_ = a.relu ? 0.f : -__builtin_inff();
+    // the grid is sized so that its thread count is a multiple of channels / 8: a thread keeps its channels
+    const int c = (int)((blockIdx.x * 256u + threadIdx.x) % (unsigned)c8n) * 8;
+    const bn_f32x8 sc = ld8f(a.scale + c), sh = ld8f(a.shift + c);
+    auto one = [&](const uint4 xw, const uint4 rw) {
+        const bn_f32x8 v = up8(xw), r = up8(rw);
+        bn_f32x8 o;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            float e = __fmaf_rn(v[i], sc[i], sh[i]);
+            if (r8) e += r[i];
+            o[i] = fmaxf(e, floor_);
+        }
+        return down8(o);
+    };
+    const uint4 none = make_uint4(0u, 0u, 0u, 0u);
+    const long long stride = gridDim.x * 256ll;
+    long long i = blockIdx.x * 256ll + threadIdx.x;
+    for (; i + stride < total; i += 2 * stride) {      // two (four with a residual) loads in flight per thread
+        const uint4 x0 = x8[i], x1 = x8[i + stride];
+        const uint4 r0 = r8 ? r8[i] : none, r1 = r8 ? r8[i + stride] : none;
+        y8[i] = one(x0, r0);
+        y8[i + stride] = one(x1, r1);
+    }
+    if (i < total) y8[i] = one(x8[i], r8 ? r8[i] : none);
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_reduce_bf16_kernel(const BnArgs a, const BnMaps16 t) {
+    __shared__ double lds[32][64][2];
+    const int cg = blockIdx.x * 64, c8 = (threadIdx.x & 7) * 8, prow = threadIdx.x >> 3;
+    const long long p0 = (long long)blockIdx.y * a.pix_per_range;
+    const long long p1 = p0 + a.pix_per_range < a.pixels ? p0 + a.pix_per_range : a.pixels;
+    double sb[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (cg + c8 < a.channels) {
+        const bn_f32x8 mean = ld8f(a.mean + cg + c8), istd = ld8f(a.invstd + cg + c8);
+        bn_f32x8 fsc = {}, fsh = {};
+        const bool from_x = a.relu == 2;
+        if (from_x) fold_affine8(a, cg + c8, mean, istd, fsc, fsh);
+        auto one = [&](const uint4 dw, const uint4 xw, const uint4 yw) {
+            bn_f32x8 d = up8(dw);
+            const bn_f32x8 v = up8(xw);
+            bn_f32x8 y = up8(yw);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if (from_x) y[i] = __fmaf_rn(v[i], fsc[i], fsh[i]);
+                if (a.relu) d[i] = y[i] > 0.f ? d[i] : 0.f;
+                sb[i] += d[i];
+                sg[i] += (double)d[i] * ((v[i] - mean[i]) * istd[i]);
+            }
+        };
+        const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+        long long p = p0 + prow;
+        for (; p + 32 < p1; p += 64) {           // six loads in flight per thread
+            const size_t o0 = p * a.channels + cg + c8, o1 = (p + 32) * a.channels + cg + c8;
+            const uint4 d0 = *reinterpret_cast<const uint4 *>(t.dy + o0), d1 = *reinterpret_cast<const uint4 *>(t.dy + o1);
+            const uint4 v0 = *reinterpret_cast<const uint4 *>(t.x + o0), v1 = *reinterpret_cast<const uint4 *>(t.x + o1);
+            const uint4 y0 = a.relu == 1 ? *reinterpret_cast<const uint4 *>(t.y_in + o0) : zero;
+            const uint4 y1 = a.relu == 1 ? *reinterpret_cast<const uint4 *>(t.y_in + o1) : zero;
+            one(d0, v0, y0);
+            one(d1, v1, y1);
+        }
+        for (; p < p1; p += 32) {
+            const size_t o = p * a.channels + cg + c8;
+            one(*reinterpret_cast<const uint4 *>(t.dy + o), *reinterpret_cast<const uint4 *>(t.x + o),
+                a.relu == 1 ? *reinterpret_cast<const uint4 *>(t.y_in + o) : zero);
+        }
+    }
+    block_partials16(a, lds, cg, c8, prow, sb, sg);
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_apply_bf16_kernel(const BnArgs a, const BnMaps16 t) {
+    const int c8n = a.channels / 8;
+    const long long total = a.pixels * c8n;
+    const float inv_m = (float)(1.0 / (double)a.pixels);
+    const uint4 *x8 = reinterpret_cast<const uint4 *>(t.x), *y8 = reinterpret_cast<const uint4 *>(t.y_in);
+    const uint4 *d8 = reinterpret_cast<const uint4 *>(t.dy);
+    uint4 *dx8 = reinterpret_cast<uint4 *>(t.dx), *dr8 = reinterpret_cast<uint4 *>(t.dres);
+    const int c = (int)((blockIdx.x * 256u + threadIdx.x) % (unsigned)c8n) * 8;   // constant per thread (grid sizing)
+    const bn_f32x8 mean = ld8f(a.mean + c), istd = ld8f(a.invstd + c);
+    bn_f32x8 db = ld8f(a.dbeta + c), dg = ld8f(a.dgamma + c), k1;
+    // dx = k1 * (dz - kb - (x - mean) * kg) with k1 = gamma * invstd, kb = dbeta / M, kg = invstd * dgamma / M
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        k1[i] = (a.gamma ? a.gamma[c + i] : 1.f) * istd[i];
+        db[i] *= inv_m;
+        dg[i] *= istd[i] * inv_m;
+    }
+    bn_f32x8 fsc = {}, fsh = {};
+    const bool from_x = a.relu == 2, with_y = a.relu == 1;
+    if (from_x) fold_affine8(a, c, mean, istd, fsc, fsh);
+    auto one = [&](long long i, const uint4 dw, const uint4 xw, const uint4 yw) {
+        bn_f32x8 d = up8(dw), o;
+        const bn_f32x8 v = up8(xw), ys = up8(yw);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (a.relu) {
+                const float y = from_x ? __fmaf_rn(v[k], fsc[k], fsh[k]) : ys[k];
+                d[k] = y > 0.f ? d[k] : 0.f;
+            }
+            o[k] = k1[k] * (d[k] - db[k] - (v[k] - mean[k]) * dg[k]);
+        }
+        if (dr8) dr8[i] = down8(d);            // (a masked copy of dy: exact)
+        dx8[i] = down8(o);
+    };
+    const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+    const long long stride = gridDim.x * 256ll;
+    long long i = blockIdx.x * 256ll + threadIdx.x;
+    for (; i + stride < total; i += 2 * stride) {      // four to six loads in flight per thread
+        const uint4 d0 = d8[i], d1 = d8[i + stride], v0 = x8[i], v1 = x8[i + stride];
+        const uint4 y0 = with_y ? y8[i] : zero, y1 = with_y ? y8[i + stride] : zero;
+        one(i, d0, v0, y0);
+        one(i + stride, d1, v1, y1);
+    }
+    if (i < total) one(i, d8[i], x8[i], with_y ? y8[i] : zero);
+}
+
+int plan16(long long pixels, int channels, BnArgs &a) {
+    SGV3D_REQUIRE(channels > 0 && channels % 8 == 0, "batchnorm (bf16 tensors): channels %% 8 == 0 required");
+    return plan(pixels, channels, a);
+}
+
+int bn_backward16(long long pixels, int channels, const void *x, const void *y, const void *dy, const float *gamma, const float *beta,
+                  const float *save_mean, const float *save_invstd, int relu, void *dx, void *dresidual, float *dgamma, float *dbeta,
+                  void *workspace, size_t workspace_bytes, void *stream) {
+    BnArgs a{};
+    if (int rc = plan16(pixels, channels, a)) return rc;
+    SGV3D_REQUIRE(x && dy && save_mean && save_invstd && dx && dgamma && dbeta && workspace, "batchnorm_train_backward_bf16: null pointer");
+    SGV3D_REQUIRE(workspace_bytes >= sgv3d_batchnorm_workspace_bytes(channels), "batchnorm_train_backward_bf16: workspace too small");
+    SGV3D_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(dx) && (!y || aligned16(y)) && (!dresidual || aligned16(dresidual)) &&
+                  aligned16(save_mean) && aligned16(save_invstd) && aligned16(dgamma) && aligned16(dbeta) && (!gamma || aligned16(gamma)) &&
+                  (!beta || aligned16(beta)) && aligned16(workspace),
+                  "batchnorm_train_backward_bf16: buffers must be 16-byte aligned");
+    a.gamma = gamma; a.beta = beta; a.mean = const_cast<float *>(save_mean); a.invstd = const_cast<float *>(save_invstd);
+    a.relu = relu; a.dgamma = dgamma; a.dbeta = dbeta;
+    a.partial = static_cast<double *>(workspace);
+    BnMaps16 t{};
+    t.x = static_cast<const unsigned short *>(x); t.y_in = static_cast<const unsigned short *>(y);
+    t.dy = static_cast<const unsigned short *>(dy); t.dx = static_cast<unsigned short *>(dx);
+    t.dres = static_cast<unsigned short *>(dresidual);
+    hipStream_t s = as_stream(stream);
+    bn_bwd_reduce_bf16_kernel<<<dim3(cdiv(channels, 64), a.ranges), 256, 0, s>>>(a, t);
+    if (int rc = check_launch("bn_bwd_reduce_bf16_kernel")) return rc;
+    bn_bwd_finalize_kernel<<<cdiv(channels, kFinCh), 256, 0, s>>>(a);
+    if (int rc = check_launch("bn_bwd_finalize_kernel")) return rc;
+    bn_bwd_apply_bf16_kernel<<<stream_blocks(pixels * (channels / 8), channels / 8), 256, 0, s>>>(a, t);
+    return check_launch("bn_bwd_apply_bf16_kernel");
+}
+
+}  // namespace
+
+extern "C" int sgv3d_batchnorm_train_forward_bf16(long long pixels, int channels, const void *x, const void *residual,
+                                                  const float *gamma, const float *beta, float *running_mean,
+                                                  float *running_var, float momentum, float eps, int relu, void *y,
+                                                  float *save_mean, float *save_invstd, void *workspace,
+                                                  size_t workspace_bytes, void *stream) {
+    BnArgs a{};
+    if (int rc = plan16(pixels, channels, a)) return rc;
+    SGV3D_REQUIRE(x && y && save_mean && save_invstd && workspace, "batchnorm_train_forward_bf16: null pointer");
+    SGV3D_REQUIRE(workspace_bytes >= sgv3d_batchnorm_workspace_bytes(channels), "batchnorm_train_forward_bf16: workspace too small");
+    SGV3D_REQUIRE(aligned16(x) && aligned16(y) && (!residual || aligned16(residual)) && aligned16(workspace),
+                  "batchnorm_train_forward_bf16: buffers must be 16-byte aligned");
+    a.gamma = gamma; a.beta = beta; a.running_mean = running_mean; a.running_var = running_var; a.mean = save_mean;
+    a.invstd = save_invstd; a.momentum = momentum; a.eps = eps; a.relu = relu;
+    a.partial = static_cast<double *>(workspace);
+    a.scale = reinterpret_cast<float *>(static_cast<char *>(workspace) + partial_bytes(channels));
+    a.shift = a.scale + channels;
+    BnMaps16 t{};
+    t.x = static_cast<const unsigned short *>(x); t.res = static_cast<const unsigned short *>(residual);
+    t.y = static_cast<unsigned short *>(y);
+    hipStream_t s = as_stream(stream);
+    bn_stats_bf16_kernel<<<dim3(cdiv(channels, 64), a.ranges), 256, 0, s>>>(a, t);
+    if (int rc = check_launch("bn_stats_bf16_kernel")) return rc;
+    bn_finalize_kernel<<<cdiv(channels, kFinCh), 256, 0, s>>>(a);
+    if (int rc = check_launch("bn_finalize_kernel")) return rc;
+    bn_apply_bf16_kernel<<<stream_blocks(pixels * (channels / 8), channels / 8), 256, 0, s>>>(a, t);
+    return check_launch("bn_apply_bf16_kernel");
+}
+
+extern "C" int sgv3d_batchnorm_train_backward_bf16(long long pixels, int channels, const void *x, const void *y, const void *dy,
+                                                   const float *gamma, const float *save_mean, const float *save_invstd, int relu,
+                                                   void *dx, void *dresidual, float *dgamma, float *dbeta, void *workspace,
+                                                   size_t workspace_bytes, void *stream) {
+    SGV3D_REQUIRE(!relu || y, "batchnorm_train_backward_bf16: the forward output is needed for the ReLU mask");
+    return bn_backward16(pixels, channels, x, y, dy, gamma, nullptr, save_mean, save_invstd, relu ? 1 : 0, dx, dresidual, dgamma, dbeta,
+                         workspace, workspace_bytes, stream);
+}
+
+extern "C" int sgv3d_batchnorm_relu_train_backward_from_x_bf16(long long pixels, int channels, const void *x, const void *dy,
+                                                               const float *gamma, const float *beta, const float *save_mean,
+                                                               const float *save_invstd, void *dx, float *dgamma, float *dbeta,
+                                                               void *workspace, size_t workspace_bytes, void *stream) {
+    return bn_backward16(pixels, channels, x, nullptr, dy, gamma, beta, save_mean, save_invstd, 2, dx, nullptr, dgamma, dbeta, workspace,
+                         workspace_bytes, stream);
+}

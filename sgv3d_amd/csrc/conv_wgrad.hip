@@ -15,6 +15,8 @@
 // (the reduction is the long axis here: 5 000 - 83 000 pixels against 64 x 64 outputs); with more than one split
 // the partial tiles go to the workspace and wgrad_reduce_kernel adds them in split order (deterministic) while
 // transposing to the OIHW layout of nn.Conv2d.weight.grad.
+#include <type_traits>
+
 #include "common.hpp"
 
 using namespace sgv3d;
@@ -506,10 +508,29 @@ __global__ __launch_bounds__(256) void interleave_phases_kernel(const PhaseArgs 
 // are what bounds it (L2), not the MFMA pipe.
 typedef __bf16 wbf16x8 __attribute__((ext_vector_type(8)));
 typedef float wf32x8 __attribute__((ext_vector_type(8)));
+typedef unsigned wu32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned wu32x4 __attribute__((ext_vector_type(4)));
 
-template <int TM, int TN>
+// The (8 pixels x 4 channels) block of a thread as bf16 TENSORS deliver it -- eight 8-byte loads, pixel j in r[j] -- to the 16-byte LDS
+// row of channel e: the eight 16-bit values are moved, not converted.
+__device__ __forceinline__ wu32x4 pixel_column16(const wu32x2 *r, int e) {
+    wu32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned w0 = r[2 * k][e >> 1], w1 = r[2 * k + 1][e >> 1];
+        o[k] = (e & 1) ? ((w0 >> 16) | (w1 & 0xffff0000u)) : ((w0 & 0xffffu) | (w1 << 16));
+    }
+    return o;
+}
+
+// T = float: f32 tensors, rounded to bf16 while staging.  T = unsigned short: bf16 tensors (bf16 activation storage); only the
+// global -> register -> LDS staging differs -- the LDS image, the fragment reads, the MFMA order, the pixel split and the reduce are the
+// same, so for one (tile, split) the result is bitwise that of the f32 form fed the upcast values.
+template <int TM, int TN, typename T = float>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const WgradArgs a) {
     constexpr int BM = 64 * TM, BN = 64 * TN, STAGE = 64;
+    constexpr bool F32 = sizeof(T) == 4;
+    constexpr unsigned ES = sizeof(T);                                      // bytes per tensor element
     constexpr int NA = 8 * (BM / 4), NB_ = 8 * (BN / 4);                    // (8 pixels x 4 channels) blocks per stage
     constexpr int B_OFF = (TM == 1 && TN == 1) ? 128 : 0;                   // 64 x 64: threads 0-127 stage dY, 128-255 stage X
     __shared__ __attribute__((aligned(16))) unsigned short sA[2][BM * STAGE];
@@ -537,7 +558,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const WgradArgs
     const int b_pg = has_b ? ib / (BN / 4) : 0, b_cq = has_b ? ib % (BN / 4) : 0;
     // channel tails: whole float4s (cin / cout % 4 == 0 is required by the entry); a quad past the layer's channels reads zeros
     const bool a_ch_ok = has_a && co0 + 4 * a_cq < a.cout, b_ch_ok = has_b && ci0 + 4 * b_cq < a.cin;
-    const unsigned y_c = (unsigned)(a.y_coff + co0 + 4 * a_cq) * 4u, x_c = (unsigned)(a.x_coff + ci0 + 4 * b_cq) * 4u;
+    const unsigned y_c = (unsigned)(a.y_coff + co0 + 4 * a_cq) * ES, x_c = (unsigned)(a.x_coff + ci0 + 4 * b_cq) * ES;
     // LDS store addresses (bytes inside a buffer): rows 4 cq + e, chunk pg at slot pg ^ key(row)
     unsigned a_st[4], b_st[4];
 #pragma unroll
@@ -552,14 +573,15 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const WgradArgs
     for (int ks = 0; ks < 4; ++ks) rd[ks] = (unsigned)(l32 * 128 + (((2 * ks + half) ^ rkey) << 4));
     const unsigned a_row0 = (unsigned)(wm * (BM / 2) * 128), b_row0 = (unsigned)(wn * (BN / 2) * 128);
 
-    f32x4n ra[8], rb[8];
+    typename std::conditional<F32, f32x4n, wu32x2>::type ra[8], rb[8];
     auto load_stage = [&](int p0) {
         // dY: pixels p0 + 8 a_pg + j
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int pix = p0 + 8 * a_pg + j;
-            const unsigned yo = (a_ch_ok && pix < pix_end) ? (unsigned)pix * (unsigned)(a.y_ld * 4) + y_c : 0xffffffffu;
-            ra[j] = __builtin_bit_cast(f32x4n, __builtin_amdgcn_raw_buffer_load_b128(y_rsrc, yo, 0, 0));
+            const unsigned yo = (a_ch_ok && pix < pix_end) ? (unsigned)pix * ((unsigned)a.y_ld * ES) + y_c : 0xffffffffu;
+            if constexpr (F32) ra[j] = __builtin_bit_cast(f32x4n, __builtin_amdgcn_raw_buffer_load_b128(y_rsrc, yo, 0, 0));
+            else ra[j] = __builtin_bit_cast(wu32x2, __builtin_amdgcn_raw_buffer_load_b64(y_rsrc, yo, 0, 0));
         }
         // X: the tap's input pixel of output pixels p0 + 8 b_pg + j (one decode per block, then a walk along the row)
         const int q0 = p0 + 8 * b_pg;
@@ -571,8 +593,9 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const WgradArgs
         for (int j = 0; j < 8; ++j) {
             const int iy = oy * a.stride - a.pad + th * a.dil, ix = ox * a.stride - a.pad + tw * a.dil;
             const bool ok = b_ch_ok && q0 + j < pix_end && iy >= 0 && iy < a.in_h && ix >= 0 && ix < a.in_w;
-            const unsigned xo = ok ? (unsigned)((img * a.in_h + iy) * a.in_w + ix) * (unsigned)(a.x_ld * 4) + x_c : 0xffffffffu;
-            rb[j] = __builtin_bit_cast(f32x4n, __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, xo, 0, 0));
+            const unsigned xo = ok ? (unsigned)((img * a.in_h + iy) * a.in_w + ix) * ((unsigned)a.x_ld * ES) + x_c : 0xffffffffu;
+            if constexpr (F32) rb[j] = __builtin_bit_cast(f32x4n, __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, xo, 0, 0));
+            else rb[j] = __builtin_bit_cast(wu32x2, __builtin_amdgcn_raw_buffer_load_b64(x_rsrc, xo, 0, 0));
             if (++ox == a.out_w) { ox = 0; if (++oy == a.out_h) { oy = 0; ++img; } }
         }
     };
@@ -581,15 +604,23 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_bf16_kernel(const WgradArgs
         if (has_a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const wf32x8 v = {ra[0][e], ra[1][e], ra[2][e], ra[3][e], ra[4][e], ra[5][e], ra[6][e], ra[7][e]};
-                *reinterpret_cast<wbf16x8 *>(pa + a_st[e]) = __builtin_convertvector(v, wbf16x8);
+                if constexpr (F32) {
+                    const wf32x8 v = {ra[0][e], ra[1][e], ra[2][e], ra[3][e], ra[4][e], ra[5][e], ra[6][e], ra[7][e]};
+                    *reinterpret_cast<wbf16x8 *>(pa + a_st[e]) = __builtin_convertvector(v, wbf16x8);
+                } else {
+                    *reinterpret_cast<wu32x4 *>(pa + a_st[e]) = pixel_column16(ra, e);
+                }
             }
         }
         if (has_b) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const wf32x8 v = {rb[0][e], rb[1][e], rb[2][e], rb[3][e], rb[4][e], rb[5][e], rb[6][e], rb[7][e]};
-                *reinterpret_cast<wbf16x8 *>(pb + b_st[e]) = __builtin_convertvector(v, wbf16x8);
+                if constexpr (F32) {
+                    const wf32x8 v = {rb[0][e], rb[1][e], rb[2][e], rb[3][e], rb[4][e], rb[5][e], rb[6][e], rb[7][e]};
+                    *reinterpret_cast<wbf16x8 *>(pb + b_st[e]) = __builtin_convertvector(v, wbf16x8);
+                } else {
+                    *reinterpret_cast<wu32x4 *>(pb + b_st[e]) = pixel_column16(rb, e);
+                }
             }
         }
     };
@@ -807,6 +838,49 @@ extern "C" int sgv3d_conv2d_backward_weight_bf16(const sgv3d_conv_desc *d, const
     if (a.wm == 2 && a.wn == 2) conv_wgrad_bf16_kernel<2, 2><<<grid, 256, 0, st>>>(a);
     else conv_wgrad_bf16_kernel<1, 1><<<grid, 256, 0, st>>>(a);
     if (int rc = check_launch("conv_wgrad_bf16_kernel")) return rc;
+    if (a.split > 1) {
+        const long long total = (long long)a.taps * a.cout * a.cin;
+        wgrad_reduce_kernel<<<cdiv(total, 256), 256, 0, st>>>(a);
+        return check_launch("wgrad_reduce_kernel");
+    }
+    return SGV3D_OK;
+}
+
+// ... reading bf16 TENSORS (bf16 activation storage: x and dy as the backbone keeps them in HBM, dw f32).  Same tiles, split, workspace
+// layout and reduce; channel counts are multiples of 4, channel strides and offsets of 8 -- the layout contract of the bf16 maps (whole
+// 16-byte units per pixel, what the BatchNorm and convolution kernels on them read); the 8-byte loads here need only multiples of 4.
+namespace {
+int fill_args_bf16_tensors(const sgv3d_conv_desc *d, int split, WgradArgs &a) {
+    if (int rc = fill_args_bf16(d, split, a)) return rc;
+    SGV3D_REQUIRE(d->x_coff % 8 == 0 && d->y_coff % 8 == 0 && d->x_ld % 8 == 0 && d->y_ld % 8 == 0,
+                  "conv2d_backward_weight_bf16_tensors: channel strides and offsets must be multiples of 8");
+    a.x_bytes /= 2; a.y_bytes /= 2;          // (2-byte elements)
+    return SGV3D_OK;
+}
+}  // namespace
+
+extern "C" size_t sgv3d_conv2d_backward_weight_bf16_tensors_workspace_bytes(const sgv3d_conv_desc *d, int split) {
+    WgradArgs a;
+    if (fill_args_bf16_tensors(d, split, a) != SGV3D_OK) return 0;
+    return a.split > 1 ? (size_t)a.split * a.taps * a.cout * a.cin * sizeof(float) : 0;
+}
+
+extern "C" int sgv3d_conv2d_backward_weight_bf16_tensors(const sgv3d_conv_desc *d, const void *x, const void *dy, float *dw, int split,
+                                                         void *workspace, size_t workspace_bytes, void *stream) {
+    WgradArgs a;
+    if (int rc = fill_args_bf16_tensors(d, split, a)) return rc;
+    SGV3D_REQUIRE(x && dy && dw, "conv2d_backward_weight_bf16_tensors: null pointer");
+    SGV3D_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0, "conv2d_backward_weight_bf16_tensors: x / dy must be 16-byte aligned");
+    const size_t need = a.split > 1 ? (size_t)a.split * a.taps * a.cout * a.cin * sizeof(float) : 0;
+    SGV3D_REQUIRE(need == 0 || (workspace && workspace_bytes >= need), "conv2d_backward_weight_bf16_tensors: workspace too small (%zu < %zu)",
+                  workspace_bytes, need);
+    // (the kernel reads the tensors through buffer resources only: the pointers are opaque to WgradArgs)
+    a.x = static_cast<const float *>(x); a.dy = static_cast<const float *>(dy); a.dw = dw; a.ws = static_cast<float *>(workspace);
+    hipStream_t st = as_stream(stream);
+    const dim3 grid(a.tiles_co * a.tiles_ci * a.taps, a.split);
+    if (a.wm == 2 && a.wn == 2) conv_wgrad_bf16_kernel<2, 2, unsigned short><<<grid, 256, 0, st>>>(a);
+    else conv_wgrad_bf16_kernel<1, 1, unsigned short><<<grid, 256, 0, st>>>(a);
+    if (int rc = check_launch("conv_wgrad_bf16_kernel(bf16 tensors)")) return rc;
     if (a.split > 1) {
         const long long total = (long long)a.taps * a.cout * a.cin;
         wgrad_reduce_kernel<<<cdiv(total, 256), 256, 0, st>>>(a);

@@ -23,6 +23,8 @@
 // wgrad3x3_bf16_reduce_kernel adds them in item order (deterministic) into OIHW.
 // Bound: MFMA bf16 (2.5 PFLOP/s dense); algorithmic 2 * 9 * pixels * cout * cin flop, HBM bytes = one read of X and dY per 64-wide
 // tile of the other operand's channels.
+#include <type_traits>
+
 #include "common.hpp"
 
 using namespace sgv3d;
@@ -35,6 +37,8 @@ typedef float f32x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kMaxBatch = 48;
 constexpr int kP = 32;                   // pixels per output row segment = k per stage (two k-steps of 16)
@@ -68,7 +72,13 @@ __device__ __forceinline__ bf16x8 tr_read8(const unsigned char *lds, unsigned of
     return __builtin_bit_cast(bf16x8, v);
 }
 
+// T = float: f32 tensors, rounded to bf16 while staging.  T = unsigned short: bf16 tensors (bf16 activation storage) -- the thread's 8
+// channels arrive as two 8-byte loads and are stored as they are; everything behind the LDS image is the same code, so for one split
+// the result is bitwise that of the f32 form fed the upcast values.
+template <typename T>
 __global__ __launch_bounds__(256, 2) void conv_wgrad3x3_bf16_kernel(const W3Args a) {
+    constexpr bool F32 = sizeof(T) == 4;
+    constexpr unsigned ES = sizeof(T);                    // bytes per tensor element
     __shared__ __attribute__((aligned(16))) unsigned char lds[2 * kDyBytes + 4 * kXBytes];
     unsigned char *const dyb = lds, *const xsb = lds + 2 * kDyBytes;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -101,18 +111,31 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3_bf16_kernel(const W3Args
     const int xpasses = (sw * 8 + 255) >> 8;
     // dY: pixel ox0 + sp, channels co0 + sc .. + 8 (two 16-byte halves, each in range or not: channel counts are multiples of 4)
     const bool dy_px_ok = ox0 + sp < a.out_w;
-    const unsigned dy_c = (unsigned)(a.y_coff + co0 + sc) * 4u;
+    const unsigned dy_c = (unsigned)(a.y_coff + co0 + sc) * ES;
     const bool dy_ok0 = dy_px_ok && co0 + sc < a.cout, dy_ok1 = dy_px_ok && co0 + sc + 4 < a.cout;
-    const unsigned x_c = (unsigned)(a.x_coff + ci0 + sc) * 4u;
+    const unsigned x_c = (unsigned)(a.x_coff + ci0 + sc) * ES;
     const bool x_ok0 = ci0 + sc < a.cin, x_ok1 = ci0 + sc + 4 < a.cin;
 
-    f32x4 rdy[2], rx[kXPasses][2];
+    typedef typename std::conditional<F32, f32x4, u32x2>::type half_t;      // 4 channels of a pixel as loaded
+    auto load4 = [](const __amdgpu_buffer_rsrc_t &rsrc, unsigned off) -> half_t {
+        if constexpr (F32) return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0));
+        else return __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rsrc, off, 0, 0));
+    };
+    auto store8 = [](unsigned char *dst, const half_t lo, const half_t hi) {
+        if constexpr (F32) {
+            const f32x8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+            *reinterpret_cast<bf16x8 *>(dst) = __builtin_convertvector(v, bf16x8);
+        } else {
+            *reinterpret_cast<u32x4 *>(dst) = __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
+        }
+    };
+    half_t rdy[2], rx[kXPasses][2];
     auto load_dy = [&](int j) {                           // output row phase + j dil
         const int oy = phase + j * a.dil;
-        const unsigned base = (unsigned)((img * a.out_h + oy) * a.out_w + ox0 + sp) * (unsigned)(a.y_ld * 4) + dy_c;
+        const unsigned base = (unsigned)((img * a.out_h + oy) * a.out_w + ox0 + sp) * ((unsigned)a.y_ld * ES) + dy_c;
         const bool row_ok = j < j1;
-        rdy[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(y_rsrc, (row_ok && dy_ok0) ? base : 0xffffffffu, 0, 0));
-        rdy[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(y_rsrc, (row_ok && dy_ok1) ? base + 16u : 0xffffffffu, 0, 0));
+        rdy[0] = load4(y_rsrc, (row_ok && dy_ok0) ? base : 0xffffffffu);
+        rdy[1] = load4(y_rsrc, (row_ok && dy_ok1) ? base + 4u * ES : 0xffffffffu);
     };
     auto load_x = [&](int v) {                            // virtual input row v: image row phase - pad + v dil
         const int iy = phase - a.pad + v * a.dil;
@@ -123,15 +146,14 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3_bf16_kernel(const W3Args
                 const int t = sp + 32 * p;
                 const int ix = ox0 - a.pad + t;
                 const bool ok = row_ok && t < sw && (unsigned)ix < (unsigned)a.in_w;
-                const unsigned base = (unsigned)((img * a.in_h + iy) * a.in_w + ix) * (unsigned)(a.x_ld * 4) + x_c;
-                rx[p][0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, (ok && x_ok0) ? base : 0xffffffffu, 0, 0));
-                rx[p][1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, (ok && x_ok1) ? base + 16u : 0xffffffffu, 0, 0));
+                const unsigned base = (unsigned)((img * a.in_h + iy) * a.in_w + ix) * ((unsigned)a.x_ld * ES) + x_c;
+                rx[p][0] = load4(x_rsrc, (ok && x_ok0) ? base : 0xffffffffu);
+                rx[p][1] = load4(x_rsrc, (ok && x_ok1) ? base + 4u * ES : 0xffffffffu);
             }
         }
     };
     auto store_dy = [&](int j) {
-        const f32x8 v = __builtin_shufflevector(rdy[0], rdy[1], 0, 1, 2, 3, 4, 5, 6, 7);
-        *reinterpret_cast<bf16x8 *>(dyb + (j & 1) * kDyBytes + img_off(sp, sc * 2)) = __builtin_convertvector(v, bf16x8);
+        store8(dyb + (j & 1) * kDyBytes + img_off(sp, sc * 2), rdy[0], rdy[1]);
     };
     auto store_x = [&](int v) {
         unsigned char *slot = xsb + (v & 3) * kXBytes;
@@ -139,10 +161,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad3x3_bf16_kernel(const W3Args
         for (int p = 0; p < kXPasses; ++p) {
             if (p < xpasses) {
                 const int t = sp + 32 * p;
-                if (t < sw) {
-                    const f32x8 w = __builtin_shufflevector(rx[p][0], rx[p][1], 0, 1, 2, 3, 4, 5, 6, 7);
-                    *reinterpret_cast<bf16x8 *>(slot + img_off(t, sc * 2)) = __builtin_convertvector(w, bf16x8);
-                }
+                if (t < sw) store8(slot + img_off(t, sc * 2), rx[p][0], rx[p][1]);
             }
         }
     };
@@ -268,8 +287,9 @@ int fill(const sgv3d_conv_desc *d, int n, int split, W3Args &a) {
 
 size_t ws_bytes(const W3Args &a, int n) { return (size_t)n * a.items * 9 * a.cout * a.cin * sizeof(float); }
 
-int launch(W3Args &a, int n, hipStream_t st) {
-    conv_wgrad3x3_bf16_kernel<<<dim3(a.tiles_co * a.tiles_ci, a.items, n), 256, 0, st>>>(a);
+int launch(W3Args &a, int n, hipStream_t st, bool bf16_tensors = false) {
+    if (bf16_tensors) conv_wgrad3x3_bf16_kernel<unsigned short><<<dim3(a.tiles_co * a.tiles_ci, a.items, n), 256, 0, st>>>(a);
+    else conv_wgrad3x3_bf16_kernel<float><<<dim3(a.tiles_co * a.tiles_ci, a.items, n), 256, 0, st>>>(a);
     if (int rc = check_launch("conv_wgrad3x3_bf16_kernel")) return rc;
     wgrad3x3_bf16_reduce_kernel<<<dim3((unsigned)cdiv(9ll * a.cout * a.cin, 256), n), 256, 0, st>>>(a);
     return check_launch("wgrad3x3_bf16_reduce_kernel");
@@ -310,4 +330,35 @@ extern "C" int sgv3d_conv2d_backward_weight_bf16_alltaps_batched(const sgv3d_con
         a.dw_list[i] = dw_list[i];
     }
     return launch(a, n, as_stream(stream));
+}
+
+// The same gradient reading bf16 TENSORS (bf16 activation storage): x, dy bf16 NHWC, dw f32.  Channel strides and offsets are multiples of
+// 8 (the layout contract of the bf16 maps; the 8-byte loads here need only multiples of 4); split, work items, workspace layout and
+// reduce as above.
+namespace {
+int fill_tensors(const sgv3d_conv_desc *d, int n, int split, W3Args &a) {
+    if (int rc = fill(d, n, split, a)) return rc;
+    SGV3D_REQUIRE(d->x_coff % 8 == 0 && d->y_coff % 8 == 0 && d->x_ld % 8 == 0 && d->y_ld % 8 == 0,
+                  "conv2d_backward_weight_bf16_alltaps_tensors: channel strides and offsets must be multiples of 8");
+    a.x_bytes /= 2; a.y_bytes /= 2;          // (2-byte elements)
+    return SGV3D_OK;
+}
+}  // namespace
+
+extern "C" size_t sgv3d_conv2d_backward_weight_bf16_alltaps_tensors_workspace_bytes(const sgv3d_conv_desc *d, int split) {
+    W3Args a;
+    if (fill_tensors(d, 1, split, a) != SGV3D_OK) return 0;
+    return ws_bytes(a, 1);
+}
+
+extern "C" int sgv3d_conv2d_backward_weight_bf16_alltaps_tensors(const sgv3d_conv_desc *d, const void *x, const void *dy, float *dw, int split,
+                                                                 void *workspace, size_t workspace_bytes, void *stream) {
+    W3Args a;
+    if (int rc = fill_tensors(d, 1, split, a)) return rc;
+    SGV3D_REQUIRE(x && dy && dw && workspace, "conv2d_backward_weight_bf16_alltaps_tensors: null pointer");
+    SGV3D_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)dy & 15) == 0, "conv2d_backward_weight_bf16_alltaps_tensors: x / dy must be 16-byte aligned");
+    SGV3D_REQUIRE(workspace_bytes >= ws_bytes(a, 1), "conv2d_backward_weight_bf16_alltaps_tensors: workspace too small (%zu < %zu)", workspace_bytes, ws_bytes(a, 1));
+    // (the kernel reads the tensors through buffer resources only: the pointers are opaque to W3Args)
+    a.x = static_cast<const float *>(x); a.dy = static_cast<const float *>(dy); a.dw = dw; a.ws = static_cast<float *>(workspace);
+    return launch(a, 1, as_stream(stream), true);
 }

@@ -82,6 +82,12 @@ TRAIN_BF16_WGRAD = _os.environ.get("SGV3D_TRAIN_BF16_WGRAD", "1") != "0"
 # ... and 3x3 / stride-1 layers may use the all-taps form (conv_wgrad3x3_bf16.hip: a workgroup owns a 64 x 64 tile for all nine taps;
 # the batched CenterHead launch always, single layers where the first-call measurement / the tune DB says so); 0: per-tap kernel only
 WGRAD_BF16_ALLTAPS = _os.environ.get("SGV3D_WGRAD_BF16_ALLTAPS", "1") != "0"
+# Mixed-precision TRAINING with bf16 activation STORAGE in the image backbone (SGV3D_TRAIN_BF16_STORAGE=1, default off): the stages of
+# backbone.img_backbone keep their activations and activation gradients as bf16 tensors in HBM -- what autocast keeps between layers
+# in the reference (--amp_backend native) -- through the bf16 BatchNorm (csrc/bn_train.hip), the bf16-tensor weight gradients
+# (csrc/conv_wgrad*.hip) and the io bits of PackedConv.  Takes effect only where train_bf16_storage_covers() says so; off, or not
+# covered: the f32 tensors of the MFMA_BF16 step, bit for bit.
+TRAIN_BF16_STORAGE = _os.environ.get("SGV3D_TRAIN_BF16_STORAGE", "0") not in ("", "0")
 # 1x1 layers with unpadded channel counts read the OIHW weight tensor itself as their packed weights (diagnostic: 0 packs a copy)
 ALIAS_1X1_WEIGHTS = _os.environ.get("SGV3D_ALIAS_1X1_WEIGHTS", "1") != "0"
 # True (SGV3D_F32X3=1): the implicit-GEMM layers compute float32-accurate products on the bf16 matrix cores -- every
@@ -253,6 +259,17 @@ def fold_bn(bn, conv_bias=None):
         if conv_bias is not None:
             shift = shift + conv_bias.float() * scale
     return scale.contiguous(), shift.contiguous()
+
+
+def train_bf16_storage_covers(channel_counts):
+    """Whether the training forward keeps the maps of a ResNet whose stages have these channel counts as bf16 tensors
+    (TRAIN_BF16_STORAGE): the mixed-precision step with bf16 weight gradients (MFMA_BF16, not the f32x3 split, TRAIN_BF16_WGRAD) and
+    16-byte bf16 pixel rows everywhere (every count a multiple of 8, and at least 16: the bf16 weight-gradient kernels take no narrower
+    layer).  Otherwise the f32-tensor path runs, silently, like the other coverage rules."""
+    if not (TRAIN_BF16_STORAGE and MFMA_BF16 and TRAIN_BF16_WGRAD) or MFMA_F32X3:
+        return False
+    counts = [int(c) for c in channel_counts]
+    return bool(counts) and all(c >= 16 and c % 8 == 0 for c in counts)
 
 
 def activation_dtype(*channel_counts):
@@ -1023,7 +1040,7 @@ def switch_state():
     return tuple(g.get(k) for k in ("AUTOTUNE", "SPLIT_K", "WINOGRAD", "FUSED_HEAD", "HEAD_PATH", "MFMA_BF16", "BF16_ACTIVATIONS",
                                     "MFMA_F32X3", "MFIRST", "WINO4", "WINO_HALF", "PATCH_BF16", "DW_BF16", "DW_DEEP", "DW_NARROW",
                                     "DW_SPLIT_K", "DW_DEEP_MAX_WGS", "PAIR_BF16", "TUNE_STREAMS", "PARALLEL_BRANCHES", "F4RES", "OCC5", "WINO4_G48", "DCN_FUSED", "WINO4_X3", "PW_X3",
-                                    "DCN_FUSED_BF16", "DCN_FUSED_TRAIN"))
+                                    "DCN_FUSED_BF16", "DCN_FUSED_TRAIN", "TRAIN_BF16_STORAGE"))
 
 
 def conv_pair_eligible(a, b, x, residual=None):

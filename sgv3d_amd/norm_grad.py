@@ -1,4 +1,5 @@
-"""Training-mode BatchNorm2d fused with the residual add and ReLU around it, on NHWC float32 CUDA tensors
+"""Training-mode BatchNorm2d fused with the residual add and ReLU around it, on NHWC float32 CUDA tensors -- or bfloat16 ones (bf16
+activation storage, hip_ops.TRAIN_BF16_STORAGE: maps bf16, everything per channel f32, the ``*_bf16`` entries)
 (csrc/bn_train.hip).  ``batch_norm_act`` is differentiable in the input, the residual and the
 affine parameters and updates the module's running statistics like ``nn.BatchNorm2d`` in training mode."""
 import os
@@ -22,21 +23,22 @@ def _ws(channels, device):
 class _BatchNormAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, weight, bias, running_mean, running_var, momentum, eps, relu):
-        assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == 4
+        assert x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and x.is_contiguous() and x.dim() == 4
         C = int(x.shape[-1])
         pixels = x.numel() // C
         if residual is not None:
-            assert residual.shape == x.shape and residual.is_contiguous() and residual.dtype == torch.float32
+            assert residual.shape == x.shape and residual.is_contiguous() and residual.dtype == x.dtype
+        sfx = "_bf16" if x.dtype == torch.bfloat16 else ""        # bf16 maps: the *_bf16 entries (channels % 8 == 0, else the library refuses)
         y = torch.empty_like(x)
         mean = torch.empty(C, dtype=torch.float32, device=x.device)
         invstd = torch.empty(C, dtype=torch.float32, device=x.device)
         ws, nws = _ws(C, x.device)
-        with torch.cuda.device(x.device), prof("batchnorm_train_forward"):
-            rc = _lib.load().sgv3d_batchnorm_train_forward(
+        with torch.cuda.device(x.device), prof("batchnorm_train_forward" + sfx):
+            rc = getattr(_lib.load(), "sgv3d_batchnorm_train_forward" + sfx)(
                 pixels, C, x.data_ptr(), _lib.ptr(residual), _lib.ptr(weight), _lib.ptr(bias), _lib.ptr(running_mean),
                 _lib.ptr(running_var), float(momentum), float(eps), 1 if relu else 0, y.data_ptr(), mean.data_ptr(),
                 invstd.data_ptr(), ws.data_ptr(), nws, _lib.stream_handle(x.device))
-        _lib.check(rc, "sgv3d_batchnorm_train_forward")
+        _lib.check(rc, "sgv3d_batchnorm_train_forward" + sfx)
         # ReLU without a residual: the backward recomputes the mask from x (sgv3d_batchnorm_relu_train_backward_from_x), y is not kept
         ctx.from_x = bool(relu) and residual is None and MASK_FROM_X
         ctx.save_for_backward(x, y if (relu and not ctx.from_x) else None, weight, mean, invstd, bias)
@@ -49,6 +51,8 @@ class _BatchNormAct(torch.autograd.Function):
     def backward(ctx, dy):
         x, y, weight, mean, invstd, bias = ctx.saved_tensors
         dy = dy.contiguous()
+        assert dy.dtype == x.dtype
+        sfx = "_bf16" if x.dtype == torch.bfloat16 else ""
         C = int(x.shape[-1])
         pixels = x.numel() // C
         dx = torch.empty_like(x)
@@ -65,19 +69,19 @@ class _BatchNormAct(torch.autograd.Function):
             if ctx.affine_versions != (None if weight is None else weight._version, None if bias is None else bias._version):
                 raise RuntimeError("batch_norm_act: the BatchNorm weight / bias were modified in place between forward and backward; the "
                                    "ReLU mask is recomputed from them (set SGV3D_BN_MASK_FROM_X=0 to keep the forward output instead)")
-            with torch.cuda.device(x.device), prof("batchnorm_train_backward"):
-                rc = _lib.load().sgv3d_batchnorm_relu_train_backward_from_x(
+            with torch.cuda.device(x.device), prof("batchnorm_train_backward" + sfx):
+                rc = getattr(_lib.load(), "sgv3d_batchnorm_relu_train_backward_from_x" + sfx)(
                     pixels, C, x.data_ptr(), dy.data_ptr(), _lib.ptr(weight), _lib.ptr(bias), mean.data_ptr(), invstd.data_ptr(),
                     dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), nws, _lib.stream_handle(x.device))
-            _lib.check(rc, "sgv3d_batchnorm_relu_train_backward_from_x")
+            _lib.check(rc, "sgv3d_batchnorm_relu_train_backward_from_x" + sfx)
             return (dx, None, dgamma if weight is not None else None, dbeta if ctx.needs_input_grad[3] else None,
                     None, None, None, None, None)
-        with torch.cuda.device(x.device), prof("batchnorm_train_backward"):
-            rc = _lib.load().sgv3d_batchnorm_train_backward(
+        with torch.cuda.device(x.device), prof("batchnorm_train_backward" + sfx):
+            rc = getattr(_lib.load(), "sgv3d_batchnorm_train_backward" + sfx)(
                 pixels, C, x.data_ptr(), _lib.ptr(y), dy.data_ptr(), _lib.ptr(weight), mean.data_ptr(), invstd.data_ptr(),
                 1 if ctx.relu else 0, dx.data_ptr(), _lib.ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), nws,
                 _lib.stream_handle(x.device))
-        _lib.check(rc, "sgv3d_batchnorm_train_backward")
+        _lib.check(rc, "sgv3d_batchnorm_train_backward" + sfx)
         return (dx, dres, dgamma if weight is not None else None, dbeta if ctx.needs_input_grad[3] else None,
                 None, None, None, None, None)
 
@@ -120,7 +124,8 @@ def _bump_version(t):
 
 
 def batch_norm_act(bn, x, residual=None, relu=False):
-    """``relu(bn(x) + residual)`` for an ``nn.BatchNorm2d`` in training mode; ``x`` / ``residual`` NHWC float32."""
+    """``relu(bn(x) + residual)`` for an ``nn.BatchNorm2d`` in training mode; ``x`` / ``residual`` NHWC float32, or both bfloat16 (the
+    result is then bfloat16 too: one rounding after the f32 arithmetic)."""
     assert bn.training and bn.track_running_stats, "training-mode BatchNorm with running statistics"
     if bn.num_batches_tracked is not None:
         if deferred_counters._open is not None and bn.momentum is not None:

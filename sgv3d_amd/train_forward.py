@@ -102,17 +102,33 @@ def _frozen_stem(r, x):
         return r.hip_stem(x)
 
 
-def resnet(r, x, use_maxpool=True):
+def resnet_storage_covers(r):
+    """Whether ``resnet`` may keep the maps of this ResNet's stages as bf16 tensors (hip_ops.TRAIN_BF16_STORAGE and its conditions; every
+    channel count a stage's convolutions read or write a multiple of 8)."""
+    counts = [c for name in r.res_layers for m in getattr(r, name).modules() if isinstance(m, nn.Conv2d) for c in (m.in_channels, m.out_channels)]
+    return hip_ops.train_bf16_storage_covers(counts)
+
+
+def resnet(r, x, use_maxpool=True, storage=None):
+    """``storage=torch.bfloat16``: the stages keep their activations -- and, through autograd, their activation gradients -- as bf16
+    tensors in HBM (bf16 activation storage; the caller checks ``resnet_storage_covers``).  The map entering stage 1 is cast once (under a
+    frozen stem it is a constant of the step), the stage outputs handed on are cast back to float32."""
     x = _frozen_stem(r, x) if r.frozen_stem() else bn(r.bn1, conv(r.conv1, x), relu=True)
     if use_maxpool:
         x = misc_grad.maxpool3x3s2(x)
+    if storage is not None:
+        x = x.to(storage)
     outs = []
     for i, name in enumerate(r.res_layers):
         for b in getattr(r, name):
             x = block(b, x)
         if i in r.out_indices:
-            outs.append(x)
+            outs.append(x if storage is None else x.float())
     return outs
+
+
+def _img_backbone(r, x):
+    return resnet(r, x, storage=torch.bfloat16 if resnet_storage_covers(r) else None)
 
 
 def secondfpn(n, feats):
@@ -202,7 +218,7 @@ def lss_fpn_forward(bb, imgs, mats_dict, want_feats=False):
     B, S, N, _, imH, imW = imgs.shape
     assert S == 1, "one sweep (every shipped config)"
     x = hip_ops.nchw_to_nhwc(imgs.reshape(B * N, 3, imH, imW).float().contiguous(), c_pad=4)
-    feats = secondfpn(bb.img_neck, resnet(bb.img_backbone, x))
+    feats = secondfpn(bb.img_neck, _img_backbone(bb.img_backbone, x))
     height, context = heightnet(bb.height_net, feats, mats_dict)
     prob = height.softmax(-1)                                              # over the D height bins (:483)
     with torch.no_grad():
@@ -262,7 +278,7 @@ def bsm_lss_fpn_forward(bb, imgs, mats_dict):
     B, S, N, _, imH, imW = imgs.shape
     assert S == 1, "one sweep (every shipped config)"
     x = hip_ops.nchw_to_nhwc(imgs.reshape(B * N, 3, imH, imW).float().contiguous(), c_pad=4)
-    feats = resnet(bb.img_backbone, x)
+    feats = _img_backbone(bb.img_backbone, x)
     n16, n8 = secondfpn(bb.img_neck_16, feats), secondfpn(bb.img_neck_8, feats)
     depth1, semantic1, context1, semantic0 = msct_head(bb.height_net, [n16, n8], mats_dict)
     height = depth1.softmax(-1)                                            # :521

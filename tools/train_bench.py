@@ -9,7 +9,7 @@ NOT the headline metric of bench.py (inference frames/s), it tracks SURVEY §8(f
 import argparse, json, os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from sgv3d_amd import hip_ops, synthetic
+from sgv3d_amd import hip_ops, synthetic, train_forward
 from sgv3d_amd.models.bev_height import BEVHeight
 from sgv3d_amd.replicas import ReplicaGroup
 from sgv3d_amd.train_step import DataParallelAdamW, reference_lr
@@ -23,6 +23,9 @@ ap.add_argument("--config", default="cfg2", choices=["cfg2", "cfg4", "cfg5", "sm
 ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"],
                 help="bf16 = mixed-precision step: every convolution product (forward, data gradient, weight gradient) on the bf16 matrix "
                      "cores with f32 accumulation; parameters, gradients, activations, BatchNorm, loss and AdamW stay f32")
+ap.add_argument("--act-storage", default="f32", choices=["f32", "bf16"],
+                help="bf16 (with --dtype bf16): the image backbone's stages keep activations and activation gradients as bf16 tensors "
+                "(hip_ops.TRAIN_BF16_STORAGE); f32: float32 tensors everywhere")
 ap.add_argument("--no-overlap", action="store_true", help="all-reduce after backward instead of from grad hooks")
 ap.add_argument("--no-dropout", action="store_true", help="Dropout(p=0) instead of the training default 0.5 (comparisons that must not depend on the random stream)")
 ap.add_argument("--trace-loss", action="store_true", help="record the loss of every timed step (a host read per step: not for timing)")
@@ -41,6 +44,7 @@ ap.add_argument("--checkpoint", default=None, help="after the timed steps: time 
 args = ap.parse_args()
 
 hip_ops.DCN_FUSED_TRAIN = not args.no_fuse_dcn
+hip_ops.TRAIN_BF16_STORAGE = args.act_storage == "bf16"
 if args.dtype == "bf16":
     hip_ops.MFMA_BF16 = True
     hip_ops.BF16_ACTIVATIONS = False        # f32 tensors between the layers (the training kernels' contract); bf16 operands only
@@ -161,6 +165,7 @@ out = {"metric": "training samples/s (forward + loss + backward + all-reduce + A
        "peak_mem_gb": torch.cuda.max_memory_allocated(dev) / 2**30, "data": "synthetic",
        "fuse_lift_splat": bool(model.backbone.fuse_lift_splat),
        "fuse_dcn": bool(hip_ops.DCN_FUSED_TRAIN and args.dtype == "bf16"),
+       "act_storage": "bf16" if train_forward.resnet_storage_covers(model.backbone.img_backbone) else "f32",
        # (a 1-rank group with SGV3D_FORCE_DIST=1 still broadcasts / all-reduces through RCCL: the single-GPU stand-in for cfg-4)
        "collectives_active": bool(opt._collectives()), "allreduces_launched_inside_backward": EARLY[0],
        "first_allreduce_launch_at_fraction_of_backward": FIRST, "bucket_mib": max(g.numel() for _, g, _ in opt.flat.buckets) * 4 / 2**20,
