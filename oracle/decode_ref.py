@@ -5,7 +5,8 @@
 PARITY UNPINNED: mmdet3d is neither vendored in the reference nor installed here and the reference has
 no fixture for this step; this follows the published algorithm.  Where the
 upstream leaves the order of equal scores to torch.topk / numpy argsort, ties go to the lower flat
-index (the device kernels do the same).
+index, then the lower class (the device kernels do the same).  float32, one rounding per operation.
+``decode_candidates`` is the candidate stage on its own (all K rows); ``decode_task`` adds mask + NMS.
 """
 import numpy as np
 
@@ -20,8 +21,10 @@ def _topk_desc(scores, k):
     return order[:k]
 
 
-def decode_task(pred, bbox_coder, test_cfg, task_id, norm_bbox=True):
-    """pred: dict of numpy NCHW maps of ONE task -> list (per sample) of dict(bboxes, scores, labels)."""
+def decode_candidates(pred, bbox_coder, norm_bbox=True):
+    """The candidate stage of ONE task (``CenterPointBBoxCoder.decode`` up to its mask): pred, a dict of numpy NCHW maps ->
+    list (per sample) of dict(boxes [K, 7|9] with z not yet lowered, scores [K], clses [K], inds [K] flat cell indices,
+    mask [K] bool), all K = max_num rows in candidate order (score descending, ties to the lower class * K + rank)."""
     heat = _sigmoid(pred['heatmap'])
     B, cat, H, W = heat.shape
     K = bbox_coder['max_num']
@@ -64,7 +67,16 @@ def decode_task(pred, bbox_coder, test_cfg, task_id, norm_bbox=True):
         if rng is not None:
             r = np.asarray(rng, np.float32)
             mask &= (boxes[:, :3] >= r[:3]).all(1) & (boxes[:, :3] <= r[3:]).all(1)
-        boxes, scores, clses = boxes[mask], scores[mask], clses[mask]
+        out.append(dict(boxes=boxes, scores=scores, clses=clses, inds=inds, mask=mask))
+    return out
+
+
+def decode_task(pred, bbox_coder, test_cfg, task_id, norm_bbox=True):
+    """pred: dict of numpy NCHW maps of ONE task -> list (per sample) of dict(bboxes, scores, labels)."""
+    out = []
+    for c in decode_candidates(pred, bbox_coder, norm_bbox):
+        mask = c['mask']
+        boxes, scores, clses = c['boxes'][mask], c['scores'][mask], c['clses'][mask]
         keep = circle_nms(np.concatenate([boxes[:, :2], scores[:, None]], 1), test_cfg['min_radius'][task_id],
                           test_cfg['post_max_size'])
         out.append(dict(bboxes=boxes[keep], scores=scores[keep], labels=clses[keep]))
@@ -78,18 +90,18 @@ def circle_nms(dets, thresh, post_max_size=83):
     suppressed = np.zeros(n, np.int32)
     keep = []
     thresh = np.float32(thresh)
+    x1, y1 = x1.astype(np.float32), y1.astype(np.float32)
     for _i in range(n):
         i = order[_i]
         if suppressed[i]:
             continue
         keep.append(i)
-        for _j in range(_i + 1, n):
-            j = order[_j]
-            if suppressed[j]:
-                continue
-            dist = np.float32((x1[i] - x1[j]) ** 2 + (y1[i] - y1[j]) ** 2)
-            if dist <= thresh:
-                suppressed[j] = 1
+        # numba's inner loop over the later candidates, as array operations: float32, one rounding per operation
+        # (a suppressed candidate never suppresses, so marking one again changes nothing)
+        j = order[_i + 1:]
+        dx, dy = x1[i] - x1[j], y1[i] - y1[j]
+        dist = dx * dx + dy * dy
+        suppressed[j[dist <= thresh]] = 1
     return np.asarray(keep[:post_max_size], np.int64)
 
 

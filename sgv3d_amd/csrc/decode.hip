@@ -13,8 +13,13 @@
 //                       score / centre-range mask
 //   3. circle_nms       greedy suppression by squared centre distance in score order, one workgroup
 //                       per sample, the inner "suppress everything after i" loop in parallel
-// Ties (equal scores) are broken by the lower flat index; the reference leaves them to torch.topk /
-// numpy argsort, i.e. unspecified.
+// Ties (equal scores) are broken by the lower flat index, then the lower class; the reference leaves
+// them to torch.topk / numpy argsort, i.e. unspecified.
+// This file is compiled with -ffp-contract=off (csrc/Makefile): the box centres and the NMS's squared
+// distance round once per operation, as torch's element-wise ops and numba's circle_nms do.  With
+// contraction `t * voxel + pc_range` became one fused multiply-add: y moved by an ulp in half of the
+// rows of the shipped coder, and with it the `dist <= radius` decision of centres that far apart.
+// The contract (ties, the strict and inclusive edges, rounding): DESIGN.md §12a.
 #include "common.hpp"
 
 using namespace sgv3d;
