@@ -1281,6 +1281,40 @@ int sgv3d_jpeg_decode(int frames, int h, int w, int max_bytes, int seq_bytes, co
                       const sgv3d_jpeg_frame *frames_dev, const uint8_t *data, long long data_len, int32_t *status,
                       void *work, size_t work_bytes, uint8_t *dst, void *stream);
 
+/* ================================================================================================
+ * Detections -> KITTI annotation rows (csrc/result2kitti.hip): RoadSideEvaluator._format_bbox + result2kitti._convert
+ * ================================================================================================ */
+
+/* HOST function: CPython's round(v, 4) bit for bit (digits = 4), or v itself (digits = -1).  Any other digits: NaN and
+ * a message for the last-error call. */
+double sgv3d_round_decimals_host(double v, int digits);
+
+/* HOST function: workspace bytes of the conversion below for a batch of `batch` samples of n rows; 0 for bad arguments. */
+size_t sgv3d_detections_to_kitti_workspace_bytes(int batch, int n);
+
+/* Rows [:counts[b]] of boxes [batch, n, 9], scores [batch, n] (f64_inputs = 0: float32, the views of the decode's packed
+ * buffer, read in place and widened exactly; 1: float64, what the results JSON of the file chain carries), labels i32
+ * [batch, n] (rows at or beyond counts[b] are never read) -> per sample the kept detections in input
+ * order, compacted from the start of its region of fields f64 [batch, max_det, 13] (alpha, x1, y1, x2, y2, h, l, w,
+ * x, y, z, rotation_y, score) and cls i32 [batch, max_det] (0 Car, 1 Pedestrian, 2 Cyclist), and the TRUE number of
+ * kept detections in kept i32 [batch]: rows beyond max_det are counted, not written.  A detection is kept when
+ * (double)score > score_thr and class_table[label] >= 0.
+ *   calib       device f64 [batch, 33]: Tr_velo_to_cam 3x4 | camera matrix 3x3 | ego2global rotation 3x3 | translation 3
+ *   class_table HOST int8 [num_classes] (1 <= num_classes <= 64; copied into the kernel's arguments): -1, 0, 1 or 2
+ *   digits      4: every value rounded as CPython's round(v, 4); -1: unrounded
+ * One launch, one workgroup per sample, no atomics: repeatable bit for bit.  Enqueue only.  Bad arguments
+ * (SGV3D_EINVAL) and a short workspace (SGV3D_ENOSPACE) are refused before any launch. */
+int sgv3d_detections_to_kitti(int batch, int n, const void *boxes, const void *scores, int f64_inputs, const int32_t *labels,
+                              const int32_t *counts, const double *calib, const int8_t *class_table, int num_classes,
+                              double score_thr, int img_w, int img_h, int max_det, int digits, void *workspace,
+                              size_t workspace_bytes, double *fields, int32_t *cls, int32_t *kept, void *stream);
+
+/* HOST function: the same conversion over host pointers, through the same per-detection function (CPU tests). */
+int sgv3d_detections_to_kitti_host(int batch, int n, const void *boxes, const void *scores, int f64_inputs,
+                                   const int32_t *labels, const int32_t *counts, const double *calib, const int8_t *class_table,
+                                   int num_classes, double score_thr, int img_w, int img_h, int max_det, int digits,
+                                   double *fields, int32_t *cls, int32_t *kept);
+
 #ifdef __cplusplus
 }
 #endif

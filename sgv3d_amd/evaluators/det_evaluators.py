@@ -79,6 +79,23 @@ class RoadSideEvaluator():
         return kitti_evaluation(pred_label_path, self.gt_label_path, current_classes=self.current_classes,
                                 metric_path=metric_path)
 
+    def evaluate_detections(self, dets, metric_path="outputs/metrics"):
+        """``evaluate`` for detections collected on the device (``device_kitti.KittiDetections``): the annotations come from
+        ``dets.annos()`` instead of label files; ground truth, ``kitti_eval``, the result file and the returned number are
+        ``kitti_evaluation``'s."""
+        from .kitti_utils import kitti_common as kitti
+        from .kitti_utils.eval import kitti_eval
+        pred_annos, image_ids = dets.annos()
+        gt_annos = kitti.get_label_annos(self.gt_label_path, image_ids=image_ids)
+        print(len(pred_annos), len(gt_annos))
+        result, ret_dict = kitti_eval(gt_annos, pred_annos, current_classes=list(self.current_classes), metric="R40")
+        mAP_3d_moderate = ret_dict["KITTI/Car_3D_moderate_strict"]
+        os.makedirs(os.path.join(metric_path, "R40"), exist_ok=True)
+        with open(os.path.join(metric_path, "R40", 'epoch_result_{}.txt'.format(round(mAP_3d_moderate, 2))), "w") as f:
+            f.write(result)
+        print(result)
+        return mAP_3d_moderate
+
     def _format_bbox(self, results, img_metas, jsonfile_prefix=None):
         annos_by_token = {}
         for sample_id, det in enumerate(results):
