@@ -1315,6 +1315,62 @@ int sgv3d_detections_to_kitti_host(int batch, int n, const void *boxes, const vo
                                    int num_classes, double score_thr, int img_w, int img_h, int max_det, int digits,
                                    double *fields, int32_t *cls, int32_t *kept);
 
+/* ================================================================================================
+ * Frame recombination (csrc/recombine.hip): the data generation of SGV3D's semi-supervised stage
+ * (scripts/data_preprocess/recombine_utils.py) on frames that are already on the device
+ * ================================================================================================ */
+
+#define SGV3D_RECOMBINE_MAX_SOURCES 3
+
+/* One generated frame.  Frames and masks are indices into a pool of uint8 RGB frames [pool, h, w, 3] and class-id masks
+ * [pool, h, w] (ids 0..6, larger values read as 6).  The frame's objects are rows [obj0, obj0 + sum(n_obj)) of the object
+ * arrays: the destination's own n_obj[0] first, then each source's n_obj[1 + s], in the order the gate walks them. */
+typedef struct sgv3d_recombine_frame {
+    int32_t dest;          /* pool index of the destination frame */
+    int32_t n_src;         /* 0..SGV3D_RECOMBINE_MAX_SOURCES */
+    int32_t src[3];        /* pool indices of the sources, in paste order */
+    int32_t obj0;
+    int32_t n_obj[4];      /* n_obj[1 + s] must be 0 for s >= n_src */
+    double minv[3][9];     /* inverse of M = K_d R_d R_s^-1 K_s^-1 per source, row-major */
+    double delta[3][3];    /* t_cam2ego of the destination minus that of the source */
+    double tr[12];         /* Tr_ego2cam of the destination, 3x4 row-major */
+    double p2[12];         /* P2 of the destination, 3x4 row-major */
+} sgv3d_recombine_frame;
+
+/* HOST function: workspace bytes of sgv3d_recombine_frames; 0 for bad arguments. */
+size_t sgv3d_recombine_workspace_bytes(int batch, int h, int w, int max_obj);
+
+/* batch generated frames in four launches (gray partials of the warped sources; reduce + beta + boxes + gate; warp +
+ * brightness shift + composite of image and mask; labels).
+ *   frames_host / frames_dev  the same `batch` descriptors on the host (checked before any launch) and on the device
+ *   images u8 [pool, h, w, 3], masks u8 [pool, h, w]                                                        device
+ *   objects f64 [total_obj, 30]: ego-frame corners [3][8] | dim h, w, l | truncated | occluded | score;   device
+ *   classes i32 [total_obj]: 0 car, 1 van, 2 truck, 3 bus, 4 pedestrian, 5 cyclist (the six the gate keeps), anything else
+ *     is a known name outside them.  The caller has filtered the objects as load_annos does and put each source's in the
+ *     order of the reference's random draw.
+ * Outputs (device): out_images u8 [batch, h, w, 3], out_masks u8 [batch, h, w] (ids 0..6), beta f64 [batch, 3] (0 for
+ * absent sources), boxes f64 [batch, max_obj, 4] the float 2-D box of every object (update_bbox_info), kept i32 [batch,
+ * max_obj] 1 for the destination's objects that stay and for accepted source objects, n_rows i32 [batch], and the label
+ * rows compacted in order: rows f64 [batch, max_obj, 15] (truncated, occluded, then rounded to four decimals: alpha, x1,
+ * y1, x2, y2, h, w, l, x, y, z, rotation_y, score) and row_info i32 [batch, max_obj, 2] (the object's index within the
+ * frame; bit 0 / 1 set when x1 / y1 is the integer 0 of Python's max(0, v)).  Entries at or beyond the frame's object
+ * count / n_rows are not written.
+ * No atomics: repeatable bit for bit.  Enqueue only.  Bad arguments (SGV3D_EINVAL: null pointers, more than three
+ * sources, h or w < 2, indices outside the pool, more objects than max_obj, non-finite homography) and a short workspace
+ * (SGV3D_ENOSPACE) are refused before any launch. */
+int sgv3d_recombine_frames(int batch, int pool, int h, int w, int max_obj, int total_obj, const sgv3d_recombine_frame *frames_host,
+                           const sgv3d_recombine_frame *frames_dev, const uint8_t *images, const uint8_t *masks, const double *objects,
+                           const int32_t *classes, void *work, size_t work_bytes, uint8_t *out_images, uint8_t *out_masks,
+                           double *beta, double *boxes, int32_t *kept, int32_t *n_rows, double *rows, int32_t *row_info,
+                           void *stream);
+
+/* HOST function: the same arithmetic over host pointers through the same per-pixel and per-object functions, summing in
+ * the kernels' order (CPU tests, sanitizer builds).  warped: NULL, or f32 [batch, 3, h, w, 3], every source warped in full. */
+int sgv3d_recombine_host(int batch, int pool, int h, int w, int max_obj, int total_obj, const sgv3d_recombine_frame *frames,
+                         const uint8_t *images, const uint8_t *masks, const double *objects, const int32_t *classes,
+                         uint8_t *out_images, uint8_t *out_masks, double *beta, double *boxes, int32_t *kept, int32_t *n_rows,
+                         double *rows, int32_t *row_info, float *warped);
+
 #ifdef __cplusplus
 }
 #endif

@@ -236,6 +236,9 @@ _PROTOS = {
                                   [c_void_p, c_size_t] + [c_void_p] * 4),
     "sgv3d_detections_to_kitti_host": (c_int, [c_int] * 2 + [c_void_p] * 2 + [c_int] + [c_void_p] * 4 + [c_int, ctypes.c_double] +
                                        [c_int] * 4 + [c_void_p] * 3),
+    "sgv3d_recombine_workspace_bytes": (c_size_t, [c_int] * 4),
+    "sgv3d_recombine_frames": (c_int, [c_int] * 6 + [c_void_p] * 7 + [c_size_t] + [c_void_p] * 9),
+    "sgv3d_recombine_host": (c_int, [c_int] * 6 + [c_void_p] * 14),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
