@@ -820,7 +820,8 @@ int sgv3d_centerhead_targets(int batch, int n_max, const float *boxes, const int
  *           data-parallel ranks (reduce_mean) before passing them on, without a host synchronisation.
  *   maps are addressed as base + b*batch_stride + c*h*w + cell (channel slices of one buffer are fine);
  *   g_* receive d(loss)/d(map) * grad_scale, addressed the same way with grad_batch_stride, or pass all six NULL
- *   for the value only;
+ *   for the value only; the call is rejected unless target_batch_stride >= num_class*h*w and pred_batch_stride (and, with
+ *   gradients, grad_batch_stride) >= max(num_class, 3)*h*w: a sample's planes must not run into the next sample's;
  *   loss_out f32[2] = (loss_heatmap, loss_bbox); code_weights host float[10];
  *   workspace sgv3d_centerhead_loss_workspace_bytes(batch) bytes. */
 size_t sgv3d_centerhead_loss_workspace_bytes(int batch);

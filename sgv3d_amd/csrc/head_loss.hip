@@ -250,9 +250,15 @@ extern "C" int sgv3d_centerhead_loss(int batch, int num_class, int h, int w, int
                   "centerhead_loss: null pointer");
     SGV3D_REQUIRE(workspace_bytes >= sgv3d_centerhead_loss_workspace_bytes(batch), "centerhead_loss: workspace too small");
     const bool grads = g_heatmap != nullptr;
-    SGV3D_REQUIRE(grads == (g_reg && g_height && g_dim && g_rot && g_vel) || (!grads && !g_reg && !g_height && !g_dim && !g_rot && !g_vel),
-                  "centerhead_loss: pass all six gradient maps or none");
+    const int n_grads = (g_heatmap != nullptr) + (g_reg != nullptr) + (g_height != nullptr) + (g_dim != nullptr) +
+                        (g_rot != nullptr) + (g_vel != nullptr);
+    SGV3D_REQUIRE(n_grads == 0 || n_grads == 6, "centerhead_loss: pass all six gradient maps or none");
     SGV3D_REQUIRE((size_t)max_objs * 8 <= 64 * 1024, "centerhead_loss: max_objs > 8192");
+    // a sample's planes must not run into the next sample's (dim has 3 channels, the heatmap num_class)
+    const long long min_stride = (long long)(num_class > 3 ? num_class : 3) * h * w;
+    SGV3D_REQUIRE(target_batch_stride >= (long long)num_class * h * w && pred_batch_stride >= min_stride &&
+                      (!grads || grad_batch_stride >= min_stride),
+                  "centerhead_loss: bad stride");
     LossArgs a{};
     a.heat = heatmap; a.target = target_heatmap; a.g_heat = g_heatmap;
     const float *maps[5] = {reg, height, dim, rot, vel};
