@@ -531,8 +531,12 @@ int sgv3d_deform_im2col3x3(int batch, int h, int w, int channels, int groups, co
 /* CenterHead second-layer convs fused over all branches (mmdet3d SeparateHead final conv, 3x3,
  * 64 -> c_k, bias; bev_height_head.py:110): hidden f32 [nb][B][H][W][hc] (one NHWC map per branch, as
  * written by sgv3d_conv2d_forward in mode SGV3D_CONV_GROUP_PLANES), weights f32 [sum_c][3][3][hc], bias
- * f32 [sum_c]; branch_of_out int32 [sum_c] maps an output channel to its branch (<= 4 per branch).
- * out f32 NCHW [B, sum_c, H, W]. */
+ * f32 [sum_c]; branch_of_out int32 [sum_c] (device memory) maps an output channel to its branch.
+ * out f32 NCHW [B, sum_c, H, W].
+ * LIMIT, not checked here (the map is device memory and this call does not synchronise): a branch has at most 4
+ * outputs, contiguous in branch_of_out, and the map is ascending.  The kernel writes the first 4 outputs that follow a
+ * branch's first one; a fifth plane stays unwritten and the call still returns SGV3D_OK.  Validate the widths on the
+ * host where the map is built (hip_ops.head_branch_of_out does).  A branch without outputs is allowed. */
 int sgv3d_head_final_conv(int batch, int h, int w, int num_branches, int hidden_ch, int total_out,
                           const float *hidden, const float *weight, const float *bias,
                           const int32_t *branch_of_out, float *out, void *stream);

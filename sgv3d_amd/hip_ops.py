@@ -1127,11 +1127,22 @@ def time_callable(fn, device, rounds=None):
     return best
 
 
+def _dense_layout(t, *dtypes):
+    """The small-layer entry points take raw pointers: a view with other strides or another dtype would be read as if it were
+    the contiguous tensor of the expected type and give a silently wrong frame."""
+    return t.is_contiguous() and t.dtype in (dtypes or (torch.float32,))
+
+
+_F32_OR_BF16 = (torch.float32, torch.bfloat16)
+
+
 def maxpool3x3s2(x, out=None):
     B, H, W, C = (int(s) for s in x.shape)
+    assert _dense_layout(x, *_F32_OR_BF16)
     oh, ow = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     if out is None:
         out = torch.empty(B, oh, ow, C, dtype=x.dtype, device=x.device)
+    assert _dense_layout(out, x.dtype) and tuple(out.shape) == (B, oh, ow, C)
     with torch.cuda.device(x.device), prof("maxpool3x3s2"):
         if x.dtype == torch.bfloat16:
             rc = _lib.load().sgv3d_maxpool3x3s2_bf16(B, H, W, C, x.data_ptr(), out.data_ptr(), _st(x))
@@ -1156,8 +1167,10 @@ def nchw_to_nhwc(x, c_pad=None, out=None):
 def nhwc_to_nchw(x, channels=None, coff=0, out=None):
     B, H, W, ld = (int(s) for s in x.shape)
     C = int(channels or ld)
+    assert _dense_layout(x)
     if out is None:
         out = torch.empty(B, C, H, W, dtype=torch.float32, device=x.device)
+    assert _dense_layout(out) and out.numel() == B * C * H * W
     with torch.cuda.device(x.device), prof("nhwc_to_nchw"):
         rc = _lib.load().sgv3d_nhwc_to_nchw(B, C, H, W, ld, int(coff), x.data_ptr(), out.data_ptr(), _st(x))
     _lib.check(rc, "sgv3d_nhwc_to_nchw")
@@ -1166,8 +1179,10 @@ def nhwc_to_nchw(x, channels=None, coff=0, out=None):
 
 def global_avgpool(x, out=None):
     B, H, W, C = (int(s) for s in x.shape)
+    assert _dense_layout(x, *_F32_OR_BF16)
     if out is None:
         out = torch.empty(B, C, dtype=torch.float32, device=x.device)
+    assert _dense_layout(out) and out.numel() == B * C
     lib = _lib.load()
     nbytes = lib.sgv3d_global_avgpool_workspace_bytes(B, C)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
@@ -1206,6 +1221,7 @@ def broadcast_channels(v, out, y_coff=0):
     """v [B,C] written to out[b, :, :, y_coff:y_coff+C] for every pixel (out NHWC)."""
     B, H, W, ld = (int(s) for s in out.shape)
     C = int(v.shape[1])
+    assert _dense_layout(v) and int(v.shape[0]) == B and _dense_layout(out, *_F32_OR_BF16)
     lib = _lib.load()
     fn = lib.sgv3d_broadcast_channels_bf16 if out.dtype == torch.bfloat16 else lib.sgv3d_broadcast_channels
     with torch.cuda.device(out.device), prof("broadcast_channels"):
@@ -1232,7 +1248,7 @@ def copy_channels(x, out, coff=0):
     """out[B,H,W,C] (contiguous) = x[B,H,W,coff:coff+C]."""
     B, H, W, ld = (int(s) for s in x.shape)
     C = int(out.shape[-1])
-    assert out.is_contiguous() and out.numel() == B * H * W * C
+    assert _dense_layout(x) and _dense_layout(out) and out.numel() == B * H * W * C
     with torch.cuda.device(x.device), prof("copy_channels"):
         rc = _lib.load().sgv3d_copy_channels(B, H * W, C, ld, int(coff), x.data_ptr(), out.data_ptr(), _st(x))
     _lib.check(rc, "sgv3d_copy_channels")
@@ -1269,6 +1285,8 @@ def add_mul_sigmoid(a, b, c, out=None):
 def bsm_compose(height_context, semantic_logits, D, ctx, sem, thr):
     """In place on height_context [B,H,W,ld]; semantic_logits [B,H,W,>=sem]."""
     B, H, W, ld = (int(s) for s in height_context.shape)
+    assert _dense_layout(height_context) and _dense_layout(semantic_logits)
+    assert tuple(semantic_logits.shape[:3]) == (B, H, W) and int(semantic_logits.shape[-1]) >= int(sem)
     with torch.cuda.device(height_context.device), prof("bsm_compose"):
         rc = _lib.load().sgv3d_bsm_compose(B, H * W, int(D), int(ctx), int(sem), ld, semantic_logits.data_ptr(),
                                           int(semantic_logits.shape[-1]), float(thr), height_context.data_ptr(),
@@ -1401,13 +1419,34 @@ def deform_im2col3x3(x, offset, groups, out=None):
     return out
 
 
+HEAD_FINAL_MAX_OUT = 4          # kHfMaxOut of csrc/misc_layers.hip: the outputs one branch of head_final_conv may have
+
+
+def head_branch_of_out(widths, device=None):
+    """The ``branch_of_out`` map of head_final_conv, int32 [sum(widths)], from the host list of outputs per branch.  Built
+    here it is ascending with each branch's outputs contiguous, which the kernel assumes; a branch wider than
+    HEAD_FINAL_MAX_OUT, whose extra planes the kernel would leave unwritten, is refused here, on the host, where the
+    widths are known (the kernel's own copy of the map lives on the device and is not read back on the frame path)."""
+    widths = [int(c) for c in widths]
+    if any(c < 0 or c > HEAD_FINAL_MAX_OUT for c in widths) or sum(widths) == 0:
+        raise ValueError(f"head_final_conv: a branch has 0..{HEAD_FINAL_MAX_OUT} outputs and the head at least one, got {widths}")
+    return torch.tensor([i for i, c in enumerate(widths) for _ in range(c)], dtype=torch.int32, device=device)
+
+
 def head_final_conv(hidden, weight, bias, branch_of_out, num_branches, hidden_ch, out=None):
-    """hidden [nb, B, H, W, hc] (one NHWC map per branch); weight [sum_c,3,3,hc]; -> NCHW [B,sum_c,H,W]."""
+    """hidden [nb, B, H, W, hc] (one NHWC map per branch); weight [sum_c,3,3,hc]; -> NCHW [B,sum_c,H,W].
+    ``branch_of_out`` int32 [sum_c] on the device: build it with head_branch_of_out.  The kernel writes the first
+    HEAD_FINAL_MAX_OUT outputs of a branch and takes them to be contiguous from the branch's first one; the map is not
+    read back here (no device-to-host sync on the frame path), so a map from elsewhere is the caller's to get right."""
     nb, B, H, W, hc = (int(s) for s in hidden.shape)
-    assert nb == num_branches and hc == hidden_ch and hidden.is_contiguous()
+    assert nb == num_branches and hc == hidden_ch and _dense_layout(hidden)
     total = int(weight.shape[0])
+    assert _dense_layout(weight) and tuple(weight.shape) == (total, 3, 3, hc)
+    assert _dense_layout(bias) and bias.numel() == total
+    assert _dense_layout(branch_of_out, torch.int32) and branch_of_out.numel() == total
     if out is None:
         out = torch.empty(B, total, H, W, dtype=torch.float32, device=hidden.device)
+    assert _dense_layout(out) and out.numel() == B * total * H * W
     with torch.cuda.device(hidden.device), prof("head_final_conv", 2.0 * B * H * W * total * 9 * hidden_ch):
         rc = _lib.load().sgv3d_head_final_conv(B, H, W, int(num_branches), int(hidden_ch), total,
                                               hidden.data_ptr(), weight.data_ptr(), bias.data_ptr(),

@@ -151,10 +151,9 @@ class BEVHeightHead(HipModule):
         # final layers: [sum_c, 3, 3, 64] + bias + branch map
         w2 = torch.cat([seq[1].weight.detach().permute(0, 2, 3, 1) for _, _, seq in br], 0)
         b2 = torch.cat([seq[1].bias.detach() for _, _, seq in br], 0)
-        branch_of_out, out_begin, slices, off = [], [0], [], 0
+        out_begin, slices, off = [0], [], 0
         for i, (t, name, seq) in enumerate(br):
             c = seq[1].out_channels
-            branch_of_out += [i] * c
             slices.append((t, name, off, c))
             off += c
             out_begin.append(off)
@@ -169,7 +168,7 @@ class BEVHeightHead(HipModule):
         if hip_ops.FUSED_HEAD and not hip_ops.MFMA_BF16 and tuple(w1.shape[1:]) == (64, 3, 3) and hc == 64:
             u_f4 = hip_ops.pack_centerhead_f4(w1.to(device).float())
         return dict(w1_bf16=w1_bf16, u_f4=u_f4, shared=conv_bn(self.shared_conv.conv, self.shared_conv.bn, True, device), first=first,
-                    w2=f(w2), b2=f(b2), branch_of_out=torch.tensor(branch_of_out, dtype=torch.int32, device=device),
+                    w2=f(w2), b2=f(b2), branch_of_out=hip_ops.head_branch_of_out([c for _, _, _, c in slices], device),
                     out_begin=ob_dev,
                     slices=slices, nb=len(br), hc=hc, total=off)
 
