@@ -6,9 +6,10 @@
  * hipStream_t passed as void* (NULL = the null stream).  No torch types.  Every entry point only
  * ENQUEUES work on `stream` (no allocation, no synchronisation, graph-capturable) and returns
  * 0 on success or a negative SGV3D_E* code; sgv3d_last_error() gives the message for the calling
- * thread.  All buffers, including workspaces, are owned by the caller, and the library retains nothing
- * between calls EXCEPT the level-1 voxel plans described under sgv3d_voxel_pooling_forward (memory the
- * library owns, freed by sgv3d_voxel_pooling_cache_clear).
+ * thread (entries marked "HOST function" run on the calling thread instead).  All buffers, including
+ * workspaces, are owned by the caller, and the library retains nothing between calls EXCEPT the level-1
+ * voxel plans described under sgv3d_voxel_pooling_forward (memory the library owns, freed by
+ * sgv3d_voxel_pooling_cache_clear).
  *
  * Each declaration cites the reference interface it replaces (paths relative to the reference repo).
  */
@@ -1375,6 +1376,55 @@ int sgv3d_recombine_host(int batch, int pool, int h, int w, int max_obj, int tot
                          const uint8_t *images, const uint8_t *masks, const double *objects, const int32_t *classes,
                          uint8_t *out_images, uint8_t *out_masks, double *beta, double *boxes, int32_t *kept, int32_t *n_rows,
                          double *rows, int32_t *row_info, float *warped);
+
+/* ================================================================================================
+ * KITTI AP tables on the device (csrc/kitti_eval_device.hip): clean_data, the greedy match, the recall thresholds and
+ * the precision / recall / orientation curves of evaluators/kitti_utils/eval.py:28-79, 157-335, 441-572 for every
+ * (metric, class, difficulty, minimum overlap) cell in one call.  sgv3d_kitti_eval_curves stays the yardstick.
+ * ================================================================================================ */
+
+/* The packed input, one buffer of 8-byte aligned sections in this order (M = num_images, TG / TD = total ground-truth /
+ * detection rows; every int32 section is rounded up to 8 bytes):
+ *   ov_off   i64 [M + 1]  offset of image m's [detections, ground truth] overlap block; ov_off[M] = total_pairs
+ *   gt_off   i32 [M + 1]  row offsets of the ground truth          dt_off  i32 [M + 1]  row offsets of the detections
+ *   tile_off i32 [M + 1]  offsets of ceil(D / 16) * ceil(G / 16) tiles per image (sgv3d_rotate_iou_pairs); [M] = num_tiles
+ *   gt       f64 [TG, 14] x1 y1 x2 y2 | alpha | location 3 | dimensions 3 | rotation_y | truncated | occluded
+ *   dt       f64 [TD, 13] alpha | x1 y1 x2 y2 | h l w | x y z | rotation_y | score   (sgv3d_detections_to_kitti's row)
+ *   gt_name  i32 [TG]     kind of the lower-cased name: 0 car, 1 pedestrian, 2 cyclist, 3 bus, 4 van, 5 person_sitting,
+ *                         6 anything else; plus 8 when the name is spelled exactly "DontCare"
+ *   dt_cls   i32 [TD]     the same kind (0..6) of a detection's name
+ * The offsets must agree with the counts: the launches trust them as sgv3d_rotate_iou_pairs does; a block the match
+ * kernels find outside the totals, or an image with more than 4096 detections, is skipped and sets status bit 1 (value 2). */
+
+/* HOST function: workspace bytes of sgv3d_kitti_eval_device; 0 for bad arguments. */
+size_t sgv3d_kitti_eval_device_workspace_bytes(int num_images, int total_gt, int total_dt, long long total_pairs, int num_classes);
+
+/* Eight launches on `stream` (prepare; rotated overlaps with box_dim 5 and 7; 2-D overlaps; match at threshold 0; sort +
+ * recall thresholds; match per threshold; finish), no host wait, integer atomics only: repeatable bit for bit.
+ *   packed        device, packed_bytes long (the layout above)
+ *   classes       HOST i32 [num_classes] (1..4 entries, each 0 car, 1 pedestrian, 2 cyclist, 3 bus)
+ *   min_overlaps  HOST f64 [2, 3, num_classes]: strict | loose, metric (2-D, BEV, 3-D), class; each >= 0
+ *   compute_aos   1: the orientation curve of the 2-D metric is computed, 0: it is zero
+ * Outputs (device): precision, recall, orientation f64 [3, num_classes, 3, 2, 41] (metric, class, difficulty, strict |
+ * loose, recall point; orientation is zero for BEV and 3-D), num_thresholds i32 [3, num_classes, 3, 2], status i32 [1]
+ * (bit 0: a cell produced more than 41 thresholds, which the host path refuses; bit 1: see above).
+ * Bad arguments (SGV3D_EINVAL: negative counts, null pointers, a class id outside 0..3, a negative minimum overlap, a
+ * packed_bytes that is not the layout's) and a short workspace (SGV3D_ENOSPACE) are refused before any launch. */
+int sgv3d_kitti_eval_device(int num_images, int total_gt, int total_dt, long long total_pairs, int num_tiles, const void *packed,
+                            size_t packed_bytes, int num_classes, const int32_t *classes, const double *min_overlaps,
+                            int compute_aos, void *workspace, size_t workspace_bytes, double *precision, double *recall,
+                            double *orientation, int32_t *num_thresholds, int32_t *status, void *stream);
+
+/* HOST function: the same tables over host pointers through the functions the kernels run (flags from the name ids, the
+ * restated selection with the 64 lanes as a loop, the sorting network, the threshold walk, the finish).  The BEV and 3-D
+ * overlaps come from the caller (f32 [total_pairs] each, the layout sgv3d_rotate_iou_pairs writes; may be NULL when
+ * total_pairs is 0); the 2-D overlaps are computed here.  thresholds: NULL, or f64 [3, num_classes, 3, 2, 41], the recall
+ * thresholds of every cell (zero beyond its count).  Checks the offsets against the totals (CPU tests, sanitizer builds). */
+int sgv3d_kitti_eval_device_host(int num_images, int total_gt, int total_dt, long long total_pairs, const void *packed,
+                                 size_t packed_bytes, const float *overlaps_bev, const float *overlaps_3d, int num_classes,
+                                 const int32_t *classes, const double *min_overlaps, int compute_aos, double *precision,
+                                 double *recall, double *orientation, int32_t *num_thresholds, int32_t *status,
+                                 double *thresholds);
 
 #ifdef __cplusplus
 }

@@ -239,6 +239,11 @@ _PROTOS = {
     "sgv3d_recombine_workspace_bytes": (c_size_t, [c_int] * 4),
     "sgv3d_recombine_frames": (c_int, [c_int] * 6 + [c_void_p] * 7 + [c_size_t] + [c_void_p] * 9),
     "sgv3d_recombine_host": (c_int, [c_int] * 6 + [c_void_p] * 14),
+    "sgv3d_kitti_eval_device_workspace_bytes": (c_size_t, [c_int] * 3 + [c_ll, c_int]),
+    "sgv3d_kitti_eval_device": (c_int, [c_int] * 3 + [c_ll, c_int, c_void_p, c_size_t, c_int, c_void_p, c_void_p, c_int,
+                                        c_void_p, c_size_t] + [c_void_p] * 6),
+    "sgv3d_kitti_eval_device_host": (c_int, [c_int] * 3 + [c_ll, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
+                                             c_int] + [c_void_p] * 6),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

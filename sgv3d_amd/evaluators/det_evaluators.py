@@ -79,12 +79,16 @@ class RoadSideEvaluator():
         return kitti_evaluation(pred_label_path, self.gt_label_path, current_classes=self.current_classes,
                                 metric_path=metric_path)
 
-    def evaluate_detections(self, dets, metric_path="outputs/metrics"):
+    def evaluate_detections(self, dets, metric_path="outputs/metrics", device_eval=False):
         """``evaluate`` for detections collected on the device (``device_kitti.KittiDetections``): the annotations come from
         ``dets.annos()`` instead of label files; ground truth, ``kitti_eval``, the result file and the returned number are
-        ``kitti_evaluation``'s."""
+        ``kitti_evaluation``'s.  ``device_eval=True`` computes the AP tables on the device (``device_eval.kitti_eval_device``)
+        instead of on the host; the text and the number are the same."""
         from .kitti_utils import kitti_common as kitti
-        from .kitti_utils.eval import kitti_eval
+        if device_eval:
+            from .device_eval import kitti_eval_device as kitti_eval
+        else:
+            from .kitti_utils.eval import kitti_eval
         pred_annos, image_ids = dets.annos()
         gt_annos = kitti.get_label_annos(self.gt_label_path, image_ids=image_ids)
         print(len(pred_annos), len(gt_annos))

@@ -21,7 +21,7 @@ from ... import _lib
 from .rotate_iou import rotate_iou_pairs
 
 __all__ = ['kitti_eval', 'eval_class', 'clean_data', 'calculate_overlaps', 'image_box_overlap', 'bev_box_overlap',
-           'd3_box_overlap', 'get_mAP', 'get_mAP_R40', 'do_eval']
+           'd3_box_overlap', 'get_mAP', 'get_mAP_R40', 'do_eval', 'eval_setup', 'eval_report']
 
 _CLASS_NAMES = ['car', 'pedestrian', 'cyclist', 'bus']          # clean_data, :29
 _MIN_HEIGHT = [40, 25, 25]
@@ -182,8 +182,9 @@ def _row(head, triple, digits):
     return head + ', '.join(f'{float(v):.{digits}f}' for v in triple)
 
 
-def kitti_eval(gt_annos, dt_annos, current_classes, eval_types=('bbox', 'bev', '3d'), metric="R40"):
-    """-> (result text, dict of 'KITTI/<class>_<3D|BEV|2D>_<difficulty>_<strict|loose>' and 'KITTI/Overall_*' values)."""
+def eval_setup(gt_annos, dt_annos, current_classes, eval_types):
+    """The part of ``kitti_eval`` before ``do_eval`` (:672-712), shared with ``device_eval.kitti_eval_device``:
+    -> (eval_types with 'aos' appended when it is evaluated, class ids, min_overlaps [2, metric, class], compute_aos)."""
     eval_types = list(eval_types)
     assert len(eval_types) > 0, 'must contain at least one evaluation type'
     if 'aos' in eval_types:
@@ -203,7 +204,18 @@ def kitti_eval(gt_annos, dt_annos, current_classes, eval_types=('bbox', 'bev', '
     compute_aos = pred_alpha and first_gt is not None and first_gt['alpha'][0] != -10
     if compute_aos and 'aos' not in eval_types:
         eval_types.append('aos')
+    return eval_types, current_classes, min_overlaps, compute_aos
+
+
+def kitti_eval(gt_annos, dt_annos, current_classes, eval_types=('bbox', 'bev', '3d'), metric="R40"):
+    """-> (result text, dict of 'KITTI/<class>_<3D|BEV|2D>_<difficulty>_<strict|loose>' and 'KITTI/Overall_*' values)."""
+    eval_types, current_classes, min_overlaps, compute_aos = eval_setup(gt_annos, dt_annos, current_classes, eval_types)
     mAPbbox, mAPbev, mAP3d, mAPaos = do_eval(gt_annos, dt_annos, current_classes, min_overlaps, eval_types, metric=metric)
+    return eval_report(current_classes, min_overlaps, compute_aos, mAPbbox, mAPbev, mAP3d, mAPaos)
+
+
+def eval_report(current_classes, min_overlaps, compute_aos, mAPbbox, mAPbev, mAP3d, mAPaos):
+    """The part of ``kitti_eval`` after ``do_eval``: AP arrays [class, difficulty, strict | loose] (or None) -> (text, dict)."""
     # The report is the wire format the AP text is compared on (evaluators/kitti_utils/eval.py:722-781): one table says which
     # metrics exist, in which order, under which label and dictionary key, with how many digits
     table = [m for m in (_Metric('bbox', '2D', mAPbbox, 4), _Metric('bev ', 'BEV', mAPbev, 4), _Metric('3d  ', '3D', mAP3d, 4),
