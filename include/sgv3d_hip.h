@@ -354,6 +354,16 @@ int sgv3d_conv_pack_weight_x3(const float *w_src, int cout, int cin, int kh, int
 int sgv3d_conv2d_x3_forward(const sgv3d_conv_desc *desc, const float *x, const void *u3_packed, const float *scale,
                             const float *bias, const float *residual, float *y, void *workspace, size_t workspace_bytes,
                             void *stream);
+/* Two sources, one output, in one launch of that kernel: a ResNet bottleneck's conv3 and the shortcut projection of its stage's first
+ * block (mmdet ResNet, layers/backbones/lss_fpn.py:296-297), y = act((A(xa) * scale_a + bias_a) + (B(xb) * scale_b + bias_b)).
+ * desc_a: source A, a 1x1 / stride 1 / unpadded layer; its output window (y_ld, y_coff), relu and tile (SGV3D_TILE_X3 | variant
+ * [| SGV3D_TILE_MFIRST]) are the launch's.  desc_b: source B, a 1x1 layer of stride 1 or 2 without padding over its own map (batch,
+ * in_h, in_w, x_ld, x_coff; its y_*, relu and tile fields are not read).  Both have cin % 32 == 0, the same cout, cout_pad, batch
+ * and output size, no split-K; u3a / u3b are their sgv3d_conv_pack_weight_x3 packs.  The result equals, bit for bit,
+ * sgv3d_conv2d_x3_forward on B (no ReLU, split_k 1) followed by sgv3d_conv2d_x3_forward on A with B's map as the residual. */
+int sgv3d_conv2d_x3_shortcut_forward(const sgv3d_conv_desc *desc_a, const float *xa, const void *u3a, const float *scale_a,
+                                     const float *bias_a, const sgv3d_conv_desc *desc_b, const float *xb, const void *u3b,
+                                     const float *scale_b, const float *bias_b, float *y, void *stream);
 size_t sgv3d_conv2d_winograd4_workspace_bytes(const sgv3d_conv_desc *desc /*host*/);
 int sgv3d_conv2d_winograd4_forward(const sgv3d_conv_desc *desc /*host*/, const float *x, const float *u_packed,
                                    const float *scale, const float *bias, const float *residual, float *y,

@@ -45,6 +45,11 @@ struct PwX3Args {
     int cin4;              // MODE 2: cin / 4
     int split_k;           // > 1: blockIdx.y owns a slice of the k-steps and stores raw partial sums to ws [split_k][M][N]
     float *ws;
+    // MODE 3 (two sources): the second source, a 1x1 / stride `stride` / no padding gather from its own map [batch][in_h][in_w][x2_ld]
+    const float *x2, *scale2, *bias2;
+    const void *w2;
+    int K2, x2_ld, x2_coff;
+    unsigned x2_bytes, w2_bytes;
 };
 
 // TAPS = false: pointwise (1x1 / stride 1): the input pixel is the output pixel.  TAPS = true: kh x kw taps (<= 32), any stride /
@@ -53,9 +58,15 @@ struct PwX3Args {
 // MODE 2 (tap-major, the weights' k order 0: k = tap * cin + ci, cin % 4 == 0, <= 64 taps): the stems -- 7x7 / stride 2 on the 4-channel
 // image and on the 80-channel BEV map.  A 16-byte chunk is 4 channels of ONE tap; the thread that owns chunk `ach` of a row walks
 // its own (tap, channel) pair from k-step to k-step (q = 8 kt + ach, tap = q / (cin / 4)); validity is a 64-bit mask per row.
+// MODE 3 (two sources, one output: a bottleneck's conv3 and the shortcut projection beside it): the MODE 0 k-loop over source A
+// (x, w, scale, bias), t = acc * scale + shift kept in registers (8 MA VGPRs), the accumulators zeroed, the same k-loop over source B
+// (x2, w2: the rows gathered at stride `stride` from a map of in_h x in_w, no padding, hence no tap mask), then
+// y = act(t + (acc * scale2 + shift2)).  Every element's sums run in k-step order per source and the two epilogue expressions are
+// those of the two separate launches (shortcut first, then conv3 with that map as its residual): the output is theirs bit for bit.
+// No split-K.
 template <int MA, int WN, int MODE>
 __global__ __launch_bounds__(64 * WN, 2) void conv_pw_x3_kernel(const PwX3Args a) {
-    constexpr bool TAPS = MODE == 1, TM = MODE == 2;
+    constexpr bool TAPS = MODE == 1, TM = MODE == 2, DUAL = MODE == 3;
     constexpr int NT = 64 * WN, BM = 16 * MA, BN = 32 * WN;
     constexpr int PLANE = BM * 64 + 64;
     constexpr int BUF = 3 * PLANE;
@@ -80,8 +91,8 @@ __global__ __launch_bounds__(64 * WN, 2) void conv_pw_x3_kernel(const PwX3Args a
     const int kb = a.K >> 5;
 
     const int tid = threadIdx.x;
-    const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.x), 0, (int)a.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.w), 0, (int)a.w_bytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.x), 0, (int)a.x_bytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.w), 0, (int)a.w_bytes, 0x00020000);
 
     // ---- pixels (f32, split here): global -> registers -> three bf16 planes in LDS.  A pass covers NT / 8 rows; lane
     // (tid >> 3, tid & 7) = 4 channels of one row
@@ -269,17 +280,61 @@ __global__ __launch_bounds__(64 * WN, 2) void conv_pw_x3_kernel(const PwX3Args a
         if ((KT) + 1 < nkt) __syncthreads();                                                              \
     } while (0)
 
-    PWX3_LOAD_X(0);
-    PWX3_LOAD_W(0, 0);
-    PWX3_STORE_X(0);
-    if (nkt > 1) PWX3_LOAD_X(1);
-    __syncthreads();
-    int kt = 0;
-    for (; kt + 1 < nkt; kt += 2) {
-        PWX3_PHASE(kt, 0, 0);
-        PWX3_PHASE(kt + 1, 1, 1);
+#define PWX3_KLOOP()                                                                                      \
+    do {                                                                                                  \
+        PWX3_LOAD_X(0);                                                                                   \
+        PWX3_LOAD_W(0, 0);                                                                                \
+        PWX3_STORE_X(0);                                                                                  \
+        if (nkt > 1) PWX3_LOAD_X(1);                                                                      \
+        __syncthreads();                                                                                  \
+        int kt = 0;                                                                                       \
+        for (; kt + 1 < nkt; kt += 2) {                                                                   \
+            PWX3_PHASE(kt, 0, 0);                                                                         \
+            PWX3_PHASE(kt + 1, 1, 1);                                                                     \
+        }                                                                                                 \
+        if (kt < nkt) PWX3_PHASE(kt, 0, 0);                                                               \
+    } while (0)
+
+    PWX3_KLOOP();
+    // MODE 3: source A's scaled and shifted sums wait in registers while the same loop runs over source B
+    [[maybe_unused]] f32x4 tkeep[MA][2];
+    if constexpr (DUAL) {
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const int col = n0 + 32 * wave + 16 * nb + 4 * g;
+            const bool on = col < a.N;
+            const f32x4 sc = (on && a.scale) ? *reinterpret_cast<const f32x4 *>(a.scale + col) : f32x4{1.f, 1.f, 1.f, 1.f};
+            const f32x4 sh = (on && a.bias) ? *reinterpret_cast<const f32x4 *>(a.bias + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ma = 0; ma < MA; ++ma) {
+                tkeep[ma][nb] = acc[ma][nb] * sc + sh;
+                acc[ma][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+        x_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.x2), 0, (int)a.x2_bytes, 0x00020000);
+        w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(a.w2), 0, (int)a.w2_bytes, 0x00020000);
+        nkt = a.K2 >> 5;
+#pragma unroll
+        for (int i = 0; i < PA; ++i) {
+            const int r = arow + RPA * i;
+            const bool live = a_on[i] && m0 + r < a.M;
+            const int m = live ? m0 + r : 0;
+            const int t = (int)((unsigned)m / (unsigned)a.out_w);
+            const int ow = m - t * a.out_w;
+            const int n = (int)((unsigned)t / (unsigned)a.out_h);
+            const int oh = t - n * a.out_h;
+            xg[i] = live ? (unsigned)((((long long)(n * a.in_h + oh * a.stride) * a.in_w + ow * a.stride) * a.x2_ld + a.x2_coff + ach * 4) * 4)
+                         : 0xffffffffu;
+        }
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const int cb = (n0 >> 4) + 2 * wave + nb;
+            wgo[nb] = (cb * 16 < a.cout_pad) ? (unsigned)(((long long)cb * nkt) * 3072 + lane * 16) : 0xffffffffu;
+        }
+        __syncthreads();                 // (the last k-step's fragment reads of buffer 0 / 1 before the first rows of source B land there)
+        PWX3_KLOOP();
     }
-    if (kt < nkt) PWX3_PHASE(kt, 0, 0);
+#undef PWX3_KLOOP
 #undef PWX3_LOAD_X
 #undef PWX3_STORE_X
 #undef PWX3_LOAD_W
@@ -304,6 +359,26 @@ __global__ __launch_bounds__(64 * WN, 2) void conv_pw_x3_kernel(const PwX3Args a
         return;
     }
     const float floor_ = a.relu ? 0.f : -__builtin_inff();
+    if constexpr (DUAL) {
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const int col = n0 + 32 * wave + 16 * nb + 4 * g;
+            if (col >= a.N) continue;
+            const f32x4 sc = a.scale2 ? *reinterpret_cast<const f32x4 *>(a.scale2 + col) : f32x4{1.f, 1.f, 1.f, 1.f};
+            const f32x4 sh = a.bias2 ? *reinterpret_cast<const f32x4 *>(a.bias2 + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ma = 0; ma < MA; ++ma) {
+                const int row = m0 + 16 * ma + l16;
+                if (row >= a.M) continue;
+                const f32x4 u = acc[ma][nb] * sc + sh;          // what the shortcut launch stores
+                f32x4 v = tkeep[ma][nb];
+                v += u;                                         // ... and conv3's epilogue adds as its residual
+                v = f32x4{fmaxf(v[0], floor_), fmaxf(v[1], floor_), fmaxf(v[2], floor_), fmaxf(v[3], floor_)};
+                *reinterpret_cast<f32x4 *>(a.y + (size_t)row * a.y_ld + a.y_coff + col) = v;
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
         const int col = n0 + 32 * wave + 16 * nb + 4 * g;
@@ -355,7 +430,8 @@ __global__ __launch_bounds__(256) void pack_weight_x3_kernel(const float *__rest
 template <int MA, int WN>
 int launch_pw(const PwX3Args &a, int mode, hipStream_t st) {
     const dim3 grid(a.tiles_m * a.tiles_n, a.split_k > 1 ? a.split_k : 1);
-    if (mode == 2) hipLaunchKernelGGL((conv_pw_x3_kernel<MA, WN, 2>), grid, dim3(64 * WN), 0, st, a);
+    if (mode == 3) hipLaunchKernelGGL((conv_pw_x3_kernel<MA, WN, 3>), grid, dim3(64 * WN), 0, st, a);
+    else if (mode == 2) hipLaunchKernelGGL((conv_pw_x3_kernel<MA, WN, 2>), grid, dim3(64 * WN), 0, st, a);
     else if (mode == 1) hipLaunchKernelGGL((conv_pw_x3_kernel<MA, WN, 1>), grid, dim3(64 * WN), 0, st, a);
     else hipLaunchKernelGGL((conv_pw_x3_kernel<MA, WN, 0>), grid, dim3(64 * WN), 0, st, a);
     return check_launch("conv_pw_x3_kernel");
@@ -452,4 +528,80 @@ extern "C" int sgv3d_conv2d_x3_forward(const sgv3d_conv_desc *d, const float *x,
     r.y = y; r.y_ld = d->y_ld; r.y_coff = d->y_coff; r.mode = SGV3D_CONV_NORMAL; r.cout = d->cout;
     r.m_h = d->out_h; r.m_w = d->out_w; r.out_h = d->out_h; r.out_w = d->out_w;
     return launch_splitk_reduce(r, st);
+}
+
+// Two sources, one output (MODE 3): y = act((A(xa) * scale_a + bias_a) + (B(xb) * scale_b + bias_b)) -- a bottleneck's conv3 (A: 1x1,
+// stride 1, desc_a, whose output window, ReLU flag and tile are the launch's) and the shortcut projection of its stage's first block
+// (B: 1x1, stride 1 or 2, no padding, desc_b) -- bit for bit what sgv3d_conv2d_x3_forward gives for B (no ReLU) and then for A with
+// B's map as the residual, without that map ever reaching memory.
+extern "C" int sgv3d_conv2d_x3_shortcut_forward(const sgv3d_conv_desc *da, const float *xa, const void *u3a, const float *scale_a,
+                                                const float *bias_a, const sgv3d_conv_desc *db, const float *xb, const void *u3b,
+                                                const float *scale_b, const float *bias_b, float *y, void *stream) {
+    SGV3D_REQUIRE(da && db && xa && xb && u3a && u3b && y, "conv2d_x3_shortcut_forward: null pointer");
+    SGV3D_REQUIRE(da->mode == SGV3D_CONV_NORMAL && db->mode == SGV3D_CONV_NORMAL && da->split_k <= 1 && db->split_k <= 1,
+                  "conv2d_x3_shortcut_forward: NHWC output, no split-K");
+    SGV3D_REQUIRE(da->kh == 1 && da->kw == 1 && da->stride == 1 && da->pad == 0 && db->kh == 1 && db->kw == 1 && db->pad == 0 &&
+                      (db->stride == 1 || db->stride == 2),
+                  "conv2d_x3_shortcut_forward: source A is 1x1 / stride 1, source B 1x1 / stride 1 or 2, neither padded");
+    SGV3D_REQUIRE(da->batch > 0 && da->in_h > 0 && da->in_w > 0 && db->in_h > 0 && db->in_w > 0 && da->cin > 0 && db->cin > 0 &&
+                      da->cout > 0 && da->cin % 32 == 0 && db->cin % 32 == 0 && da->cout % 4 == 0,
+                  "conv2d_x3_shortcut_forward: cin %% 32 == 0 on both sources, cout %% 4 == 0 (cin=%d / %d cout=%d)", da->cin, db->cin,
+                  da->cout);
+    SGV3D_REQUIRE(da->cout == db->cout && da->cout_pad == db->cout_pad, "conv2d_x3_shortcut_forward: the sources' cout differ (%d / %d)",
+                  da->cout, db->cout);
+    SGV3D_REQUIRE(da->out_h == da->in_h && da->out_w == da->in_w && db->out_h == (db->in_h - 1) / db->stride + 1 &&
+                      db->out_w == (db->in_w - 1) / db->stride + 1,
+                  "conv2d_x3_shortcut_forward: output size does not match the geometry");
+    SGV3D_REQUIRE(da->batch == db->batch && da->out_h == db->out_h && da->out_w == db->out_w,
+                  "conv2d_x3_shortcut_forward: the sources' output geometries differ (%dx%dx%d / %dx%dx%d)", da->batch, da->out_h,
+                  da->out_w, db->batch, db->out_h, db->out_w);
+    SGV3D_REQUIRE(((da->x_ld | da->x_coff | da->y_ld | da->y_coff | db->x_ld | db->x_coff) & 3) == 0,
+                  "conv2d_x3_shortcut_forward: leading dimensions and channel offsets must be multiples of 4");
+    SGV3D_REQUIRE(da->x_ld >= da->x_coff + da->cin && db->x_ld >= db->x_coff + db->cin && da->y_ld >= da->y_coff + da->cout &&
+                      da->x_coff >= 0 && db->x_coff >= 0 && da->y_coff >= 0,
+                  "conv2d_x3_shortcut_forward: leading dimension too small");
+    SGV3D_REQUIRE(da->cout_pad >= da->cout && da->cout_pad % 32 == 0,
+                  "conv2d_x3_shortcut_forward: desc.cout_pad = rows of the x3 weights (a multiple of 32)");
+    SGV3D_REQUIRE(((reinterpret_cast<uintptr_t>(xa) | reinterpret_cast<uintptr_t>(xb) | reinterpret_cast<uintptr_t>(y) |
+                    reinterpret_cast<uintptr_t>(scale_a) | reinterpret_cast<uintptr_t>(bias_a) | reinterpret_cast<uintptr_t>(scale_b) |
+                    reinterpret_cast<uintptr_t>(bias_b) | reinterpret_cast<uintptr_t>(u3a) | reinterpret_cast<uintptr_t>(u3b)) & 15) == 0,
+                  "conv2d_x3_shortcut_forward: pointers must be 16-B aligned");
+    const long long M = (long long)da->batch * da->out_h * da->out_w;
+    const long long xab = M * da->x_ld * 4, xbb = (long long)db->batch * db->in_h * db->in_w * db->x_ld * 4;
+    const long long wab = (long long)da->cout_pad * da->cin * 6, wbb = (long long)db->cout_pad * db->cin * 6;
+    SGV3D_REQUIRE(M < 0x7fffffffLL && xab < 0xf0000000LL && xbb < 0xf0000000LL && wab < 0xf0000000LL && wbb < 0xf0000000LL,
+                  "conv2d_x3_shortcut_forward: operands larger than 3.75 GiB");
+    const int variant = da->tile & 15;
+    SGV3D_REQUIRE((da->tile & SGV3D_TILE_X3) && (variant & 3) < 3 && (variant & 12) != 12,
+                  "conv2d_x3_shortcut_forward: desc_a.tile = SGV3D_TILE_X3 | variant, variant in {0,1,2, 4,5,6, 8,9,10}");
+    PwX3Args a{};
+    a.x = xa; a.w = u3a; a.scale = scale_a; a.bias = bias_a; a.res = nullptr; a.y = y;
+    a.M = (int)M; a.K = da->cin; a.N = da->cout;
+    a.x_ld = da->x_ld; a.x_coff = da->x_coff; a.y_ld = da->y_ld; a.y_coff = da->y_coff; a.res_ld = 0; a.relu = da->relu;
+    a.cout_pad = da->cout_pad;
+    a.mfirst = (da->tile & SGV3D_TILE_MFIRST) ? 1 : 0;
+    a.x_bytes = (unsigned)xab; a.w_bytes = (unsigned)wab;
+    a.in_h = db->in_h; a.in_w = db->in_w; a.out_h = db->out_h; a.out_w = db->out_w;          // the gather of source B
+    a.kh = 1; a.kw = 1; a.stride = db->stride; a.pad = 0; a.dil = 1;
+    a.cin4 = da->cin / 4;
+    a.x2 = xb; a.w2 = u3b; a.scale2 = scale_b; a.bias2 = bias_b;
+    a.K2 = db->cin; a.x2_ld = db->x_ld; a.x2_coff = db->x_coff;
+    a.x2_bytes = (unsigned)xbb; a.w2_bytes = (unsigned)wbb;
+    const int bm = 32 << (variant & 3), bn = (variant & 8) ? 256 : (variant & 4) ? 64 : 128;
+    a.tiles_m = (int)cdiv(M, bm);
+    a.tiles_n = cdiv(da->cout, bn);
+    a.split_k = 1;
+    a.ws = nullptr;
+    hipStream_t st = as_stream(stream);
+    switch (variant) {
+        case 0: return launch_pw<2, 4>(a, 3, st);
+        case 1: return launch_pw<4, 4>(a, 3, st);
+        case 2: return launch_pw<8, 4>(a, 3, st);
+        case 4: return launch_pw<2, 2>(a, 3, st);
+        case 5: return launch_pw<4, 2>(a, 3, st);
+        case 6: return launch_pw<8, 2>(a, 3, st);
+        case 8: return launch_pw<2, 8>(a, 3, st);
+        case 9: return launch_pw<4, 8>(a, 3, st);
+        default: return launch_pw<8, 8>(a, 3, st);
+    }
 }

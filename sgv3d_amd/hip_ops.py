@@ -1040,7 +1040,7 @@ def switch_state():
     return tuple(g.get(k) for k in ("AUTOTUNE", "SPLIT_K", "WINOGRAD", "FUSED_HEAD", "HEAD_PATH", "MFMA_BF16", "BF16_ACTIVATIONS",
                                     "MFMA_F32X3", "MFIRST", "WINO4", "WINO_HALF", "PATCH_BF16", "DW_BF16", "DW_DEEP", "DW_NARROW",
                                     "DW_SPLIT_K", "DW_DEEP_MAX_WGS", "PAIR_BF16", "TUNE_STREAMS", "PARALLEL_BRANCHES", "F4RES", "OCC5", "WINO4_G48", "DCN_FUSED", "WINO4_X3", "PW_X3",
-                                    "DCN_FUSED_BF16", "DCN_FUSED_TRAIN", "TRAIN_BF16_STORAGE"))
+                                    "DCN_FUSED_BF16", "DCN_FUSED_TRAIN", "TRAIN_BF16_STORAGE", "SHORTCUT_X3"))
 
 
 def conv_pair_eligible(a, b, x, residual=None):
@@ -1098,6 +1098,137 @@ def conv_pair_choice(a, b, x, residual=None):
     TUNE_DB[sig] = [1 if t1 < t2 else 0, 0]
     _COMMITTED_SIGS.discard(sig)
     return t1 < t2
+
+
+# fp32 path: a bottleneck's conv3 and the shortcut projection of its stage's first block as ONE launch of the f32x3 implicit-GEMM kernel
+# (csrc/conv_pw_x3.hip MODE 3, sgv3d_conv2d_x3_shortcut_forward): the shortcut map is never written or read back.  0
+# (SGV3D_SHORTCUT_X3=0): always two launches.
+SHORTCUT_X3 = _os.environ.get("SGV3D_SHORTCUT_X3", "1") != "0"
+
+
+def conv_shortcut_eligible(c3, ds, mid, x):
+    """``c3`` (1x1 / stride 1, the bottleneck's last layer, applied to ``mid``) and ``ds`` (1x1 / stride 1 or 2, no ReLU, the shortcut
+    projection, applied to the block's input ``x``) with the same output shape, f32 NHWC tensors, cin % 32 == 0 on both, in the fp32
+    mode with the f32x3 pointwise kernel enabled: the pair the two-source launch (``conv_shortcut_x3``) covers."""
+    if not (SHORTCUT_X3 and PW_X3 and not MFMA_BF16 and not MFMA_F32X3):
+        return False
+    if c3.transposed or ds.transposed or mid.dtype != torch.float32 or x.dtype != torch.float32:
+        return False
+    one = lambda c: c.kh == 1 and c.kw == 1 and c.pad == 0 and c.cin % 32 == 0
+    if not (one(c3) and one(ds) and c3.stride == 1 and ds.stride in (1, 2) and not ds.relu and c3.cout == ds.cout and c3.cout % 4 == 0):
+        return False
+    B, H, W, x_ld = (int(v) for v in x.shape)
+    return (tuple(int(v) for v in mid.shape[:3]) == (B,) + ds.out_hw(H, W) and int(mid.shape[-1]) % 4 == 0 and x_ld % 4 == 0
+            and int(mid.shape[-1]) >= c3.cin and x_ld >= ds.cin)
+
+
+def _shortcut_rule_tile(gemm_m, gemm_n):
+    """The fixed rule's tile of the two-source launch: 128 channels per workgroup, the largest m-tile of 128 / 64 / 32 pixels that
+    still gives two workgroups to each of the 256 CUs (the smallest otherwise)."""
+    plain = {PW_X3_DIMS[t]: t for t in PW_X3_TILES if not TILES[t].mfirst}
+    for bm in (128, 64):
+        if -(-gemm_m // bm) * -(-gemm_n // 128) >= 512:
+            return plain[bm, 128]
+    return plain[32, 128]
+
+
+def _shortcut_tiles(gemm_m, gemm_n):
+    """The tiles of the two-source launch worth timing: the pointwise kernel's shapes under the rules of the per-layer candidate
+    list (at least ~96 workgroups, 64-channel tiles only for small grids, 256-channel ones only where cout has them, m-tile first only
+    with several channel tiles) -- without 128 x 64, the one instantiation of the two-source form that spills registers."""
+    out = []
+    for t in PW_X3_TILES:
+        bm, bn = PW_X3_DIMS[t]
+        wgs = -(-gemm_m // bm) * -(-gemm_n // bn)
+        if (bm, bn) == (128, 64) or (bn == 256 and gemm_n < 256) or wgs < 96:
+            continue
+        if (bn >= 128 or gemm_n <= 64 or wgs < 1024) and (not TILES[t].mfirst or (MFIRST and gemm_n > bn)):
+            out.append(t)
+    return tuple(out) or (_shortcut_rule_tile(gemm_m, gemm_n),)
+
+
+def conv_shortcut_x3(c3, ds, mid, x, out=None, tile=None):
+    """``c3(mid, residual=ds(x))`` in one launch, bit for bit what the two f32x3 launches (split-K 1) give.  ``tile``: a host id of
+    the pw_x3 family (default: the fixed rule's)."""
+    B, H, W, x_ld = (int(v) for v in x.shape)
+    oh, ow = ds.out_hw(H, W)
+    assert mid.is_contiguous() and x.is_contiguous() and tuple(int(v) for v in mid.shape[:3]) == (B, oh, ow)
+    if out is None:
+        out = torch.empty(B, oh, ow, c3.cout, dtype=torch.float32, device=x.device)
+    gemm_m = B * oh * ow
+    T = TILES[int(tile or _shortcut_rule_tile(gemm_m, c3.cout))]
+    if T.family != "pw_x3":
+        raise _lib.SGV3DError(f"conv_shortcut_x3: tile {T.id} is not a tile of the f32x3 pointwise kernel")
+    da, db = ConvDesc(), ConvDesc()
+    for d, c, (h, w), ld in ((da, c3, (oh, ow), int(mid.shape[-1])), (db, ds, (H, W), x_ld)):
+        d.batch, d.in_h, d.in_w, d.cin = B, h, w, c.cin
+        d.out_h, d.out_w, d.cout = oh, ow, c.cout
+        d.kh, d.kw, d.stride, d.pad, d.dil = 1, 1, c.stride, 0, 1
+        d.x_ld, d.x_coff, d.y_ld, d.y_coff, d.res_ld = ld, 0, int(out.shape[-1]), 0, 0
+        d.relu, d.mode, d.split_k, d.tile = (1 if c.relu else 0), CONV_NORMAL, 1, T.abi
+        d.k_pad, d.k_order = c.k_pad, c.k_order
+    ua, ub = c3._form(T.form), ds._form(T.form)
+    da.cout_pad, db.cout_pad = c3.pw_x3_cout_pad, ds.pw_x3_cout_pad
+    flops = 2.0 * gemm_m * (c3.cout_real * c3.cin_real + ds.cout_real * ds.cin_real)
+    nbytes = 4.0 * (gemm_m * c3.cin_real + B * H * W * ds.cin_real + c3.cout_real * c3.cin_real + ds.cout_real * ds.cin_real
+                    + gemm_m * c3.cout_real)
+    name, extra = "conv_pw_x3_shortcut", None
+    if PROFILE_DETAIL:
+        name += f"|{B}x{oh}x{ow}x{c3.cin}->{c3.cout} k1 s1 + {B}x{H}x{W}x{ds.cin}->{ds.cout} k1 s{ds.stride}"
+    if PROFILE is not None:
+        mfma = 2.0 * gemm_m * c3.cout * (c3.cin + ds.cin)
+        extra = {"symbol": f"conv_pw_x3_kernel<{T.bm // 16}, {T.bn // 32}, 3>", "mfma_flops": mfma, "bf16_mfma_flops": 6 * mfma}
+    with torch.cuda.device(x.device), prof(name, flops, nbytes, extra):
+        rc = _lib.load().sgv3d_conv2d_x3_shortcut_forward(
+            ctypes.byref(da), mid.data_ptr(), ua.data_ptr(), _lib.ptr(c3.scale), _lib.ptr(c3.shift),
+            ctypes.byref(db), x.data_ptr(), ub.data_ptr(), _lib.ptr(ds.scale), _lib.ptr(ds.shift), out.data_ptr(), _st(x))
+    _lib.check(rc, "sgv3d_conv2d_x3_shortcut_forward")
+    return out
+
+
+def conv_shortcut_signature(c3, ds, x):
+    B, H, W, _ = (int(v) for v in x.shape)
+    return f"pair|shortcut|{c3.cout}x{c3.cin}+{ds.cin}s{ds.stride}|{B}x{H}x{W}|r{int(c3.relu)}|ts{TUNE_STREAMS}"
+
+
+def conv_shortcut_choice(c3, ds, mid, x):
+    """The host tile id to run ``conv_shortcut_x3`` with, or 0 when ``c3(mid, residual=ds(x))`` with the per-layer choices is the
+    faster way (or the pair is not covered).  Measured once per pair and input shape under the load the pipeline runs -- the fused
+    launch with each of its tiles against the two launches -- and kept in the tune DB under a ``pair|shortcut|`` signature as
+    [fused or not, the fused launch's tile].  The fixed rule (SGV3D_NO_AUTOTUNE, deterministic mode, a capture that meets a new
+    signature): fused, with ``_shortcut_rule_tile``."""
+    if not conv_shortcut_eligible(c3, ds, mid, x):
+        return 0
+    gemm_m, gemm_n = int(mid.shape[0]) * int(mid.shape[1]) * int(mid.shape[2]), c3.cout
+    rule = _shortcut_rule_tile(gemm_m, gemm_n)
+    if not AUTOTUNE:                                         # the documented fixed rule: no recorded measurement is consulted
+        return rule
+    sig = conv_shortcut_signature(c3, ds, x)
+    if sig in TUNE_DB and not (sig in _COMMITTED_SIGS and not _is_gfx950(x.device)):
+        on, t = (int(v) for v in TUNE_DB[sig])
+        if not on:
+            return 0
+        return t if t in PW_X3_TILES else rule
+    if torch.cuda.is_current_stream_capturing() or deterministic():
+        return rule
+    TUNE_STATS["measured"] += 1
+    out = torch.empty(tuple(mid.shape[:3]) + (c3.cout,), dtype=torch.float32, device=x.device)
+    two = lambda: c3(mid, out, residual=ds(x))
+    two()
+    t2 = time_callable(two, x.device)
+    best, t1 = 0, None
+    for t in _shortcut_tiles(gemm_m, gemm_n):
+        one = lambda: conv_shortcut_x3(c3, ds, mid, x, out, tile=t)
+        one()
+        dt = time_callable(one, x.device)
+        if TUNE_VERBOSE:
+            print(f"[tune] {sig}: fused tile {t}: {dt * 1e3 / TUNE_ROUNDS:.1f} us (two launches {t2 * 1e3 / TUNE_ROUNDS:.1f} us)", flush=True)
+        if t1 is None or dt < t1:
+            best, t1 = t, dt
+    on = t1 < t2
+    TUNE_DB[sig] = [1, best] if on else [0, 0]
+    _COMMITTED_SIGS.discard(sig)
+    return best if on else 0
 
 
 def time_callable(fn, device, rounds=None):

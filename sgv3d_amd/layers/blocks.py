@@ -147,6 +147,15 @@ class Bottleneck(HipModule):
                 if act_dtype == torch.bfloat16 and hip_ops.conv_pair_eligible(s['c2'], s['c3'], o):
                     return o, None                               # (the fused pair needs the residual: finished after the join)
                 return o, s['c2'](o, out_dtype=act_dtype)
+            if (act_dtype is None and hip_ops.SHORTCUT_X3 and hip_ops.PW_X3 and not hip_ops.MFMA_BF16 and not hip_ops.MFMA_F32X3
+                    and not hip_ops.PARALLEL_BRANCHES):
+                # fp32: conv3 and the shortcut projection as one two-source launch where that is the faster way (the shortcut map is
+                # then neither written nor read back)
+                mid = s['c2'](s['c1'](x))
+                t = hip_ops.conv_shortcut_choice(s['c3'], s['ds'], mid, x)
+                if t:
+                    return hip_ops.conv_shortcut_x3(s['c3'], s['ds'], mid, x, tile=t)
+                return s['c3'](mid, residual=s['ds'](x))
             (out, mid), identity = hip_ops.run_parallel(x.device, (main, lambda: s['ds'](x, out_dtype=act_dtype)))
             if mid is not None:
                 return s['c3'](mid, residual=identity, out_dtype=act_dtype)
