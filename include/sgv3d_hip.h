@@ -1298,6 +1298,45 @@ int sgv3d_jpeg_decode(int frames, int h, int w, int max_bytes, int seq_bytes, co
                       void *work, size_t work_bytes, uint8_t *dst, void *stream);
 
 /* ================================================================================================
+ * JPEG encoding (csrc/jpeg_encode.hip): uint8 RGB frames -> the files Pillow's save(format='JPEG', quality=q,
+ * subsampling=s, restart_marker_blocks=r) writes (libjpeg-turbo, optimize and progressive off), byte for byte
+ * ================================================================================================ */
+
+#define SGV3D_JPEG_ENC_HEADER_MAX 640 /* bytes a header buffer must hold (623 are used, 629 with a restart interval) */
+/* Per-frame status of sgv3d_jpeg_encode (0: the file was written). */
+#define SGV3D_JPEG_ENC_EOVERFLOW 1    /* the file would be longer than max_bytes: length 0, nothing written */
+
+/* Settings shared by the entries below: h, w in 1..65535; quality 1..100 (libjpeg's scaling of the Annex-K tables,
+ * baseline forced); (hs, vs) the luma sampling (1, 1) 4:4:4, (2, 1) 4:2:2 or (2, 2) 4:2:0; restart: the restart interval
+ * in MCUs, 0 (none) .. 65535.  Anything else is SGV3D_EINVAL with a message that names the value. */
+
+/* HOST function: the bytes from SOI to the end of SOS (SOI, APP0 JFIF 1.01, two DQT, SOF0, four DHT with the Annex-K
+ * tables, DRI when restart != 0, SOS) into header[SGV3D_JPEG_ENC_HEADER_MAX], their number into *header_len, and, unless
+ * quant is NULL, the luma and chroma quantisation tables in natural order into quant u16 [2][64]. */
+int sgv3d_jpeg_encode_header(int h, int w, int quality, int hs, int vs, int restart, uint8_t *header, int *header_len,
+                             uint16_t *quant);
+
+/* HOST function: workspace bytes of sgv3d_jpeg_encode; 0 for bad arguments (frames 1..4096, max_bytes 1..2^26). */
+size_t sgv3d_jpeg_encode_workspace_bytes(int frames, int h, int w, int hs, int vs, int restart, int max_bytes);
+
+/* src u8 [frames, h, w, 3] RGB (device) -> the files, compacted one after the other from the start of `files` (device),
+ * file f at the sum of the lengths before it, each rounded up to 16; lengths i32 [frames] and status i32 [frames]
+ * (device).  A file that would be longer than max_bytes gets status SGV3D_JPEG_ENC_EOVERFLOW and length 0, takes no room
+ * and leaves the other frames as they are.  files_bytes >= frames * roundup16(max_bytes); only the bytes of the files
+ * themselves are written.  work: device, 16-byte aligned, sgv3d_jpeg_encode_workspace_bytes long; the call clears what it
+ * accumulates into.  Seven launches on `stream` whatever the batch and the data (transform, size, scan, pack, ffcount,
+ * layout, stuff), no host wait, integer atomicOr only: repeatable bit for bit.  Bad arguments (SGV3D_EINVAL) and a short
+ * workspace (SGV3D_ENOSPACE) are refused before any launch. */
+int sgv3d_jpeg_encode(int frames, int h, int w, int quality, int hs, int vs, int restart, int max_bytes, const uint8_t *src,
+                      void *work, size_t work_bytes, uint8_t *files, long long files_bytes, int32_t *lengths, int32_t *status,
+                      void *stream);
+
+/* HOST function: the same files over host pointers through the functions the kernels run, one work item after the other
+ * (CPU tests, sanitizer builds). */
+int sgv3d_jpeg_encode_host(int frames, int h, int w, int quality, int hs, int vs, int restart, int max_bytes, const uint8_t *src,
+                           uint8_t *files, long long files_bytes, int32_t *lengths, int32_t *status);
+
+/* ================================================================================================
  * Detections -> KITTI annotation rows (csrc/result2kitti.hip): RoadSideEvaluator._format_bbox + result2kitti._convert
  * ================================================================================================ */
 

@@ -231,6 +231,10 @@ _PROTOS = {
     "sgv3d_jpeg_parse": (c_int, [c_void_p, c_size_t, c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "sgv3d_jpeg_workspace_bytes": (c_size_t, [c_int] * 5),
     "sgv3d_jpeg_decode": (c_int, [c_int] * 5 + [c_void_p] * 3 + [c_ll] + [c_void_p] * 2 + [c_size_t] + [c_void_p] * 2),
+    "sgv3d_jpeg_encode_header": (c_int, [c_int] * 6 + [c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    "sgv3d_jpeg_encode_workspace_bytes": (c_size_t, [c_int] * 7),
+    "sgv3d_jpeg_encode": (c_int, [c_int] * 8 + [c_void_p, c_void_p, c_size_t, c_void_p, c_ll, c_void_p, c_void_p, c_void_p]),
+    "sgv3d_jpeg_encode_host": (c_int, [c_int] * 8 + [c_void_p, c_void_p, c_ll, c_void_p, c_void_p]),
     "sgv3d_round_decimals_host": (ctypes.c_double, [ctypes.c_double, c_int]),
     "sgv3d_detections_to_kitti_workspace_bytes": (c_size_t, [c_int] * 2),
     "sgv3d_detections_to_kitti": (c_int, [c_int] * 2 + [c_void_p] * 2 + [c_int] + [c_void_p] * 4 + [c_int, ctypes.c_double] + [c_int] * 4 +

@@ -370,19 +370,28 @@ class FrameRecombiner:
         return RecombineResult(out_images, out_masks, host, ev, layout, names, M)
 
 
-def write(root, frame_id, image, mask, dest, lines, img_path="training/image_2"):
+def write(root, frame_id, image, mask, dest, lines, img_path="training/image_2", encoded=None):
     """``save_kitti_format`` of one generated frame: ``calib``, ``denorm``, ``label_2`` and ``mask_image`` (ids x 40, three
     channels, .npy) under ``root/training`` and the image under ``root/img_path`` (written through Pillow: the encoded
     bytes are Pillow's, not OpenCV's).  ``image`` u8 [H, W, 3] RGB and ``mask`` u8 [H, W] are host arrays or tensors;
-    ``dest`` carries the generated frame's ``Tr_ego2cam`` and ``P2``."""
-    from PIL import Image
-    image = np.asarray(image.cpu() if hasattr(image, 'cpu') else image)
+    ``dest`` carries the generated frame's ``Tr_ego2cam`` and ``P2``.  ``encoded``: the frame's JPEG file as bytes (one of
+    ``JpegEncoder(...)(frames).files()``): written as the .jpg as it is, and ``image`` is neither downloaded nor encoded
+    here (it may be None)."""
+    if encoded is None:
+        from PIL import Image
+        image = np.asarray(image.cpu() if hasattr(image, 'cpu') else image)
+    elif not isinstance(encoded, (bytes, bytearray, memoryview)) or bytes(encoded[:2]) != b'\xff\xd8':
+        raise ValueError("write: encoded must be the bytes of a JPEG file")
     mask = np.asarray(mask.cpu() if hasattr(mask, 'cpu') else mask)
     for sub in ("denorm", "calib", "label_2", "mask_image"):
         os.makedirs(os.path.join(root, "training", sub), exist_ok=True)
     os.makedirs(os.path.join(root, img_path), exist_ok=True)
     np.save(os.path.join(root, "training", "mask_image", frame_id + ".npy"), np.repeat(mask[:, :, None], 3, axis=2) * 40)
-    Image.fromarray(image).save(os.path.join(root, img_path, frame_id + ".jpg"))
+    if encoded is None:
+        Image.fromarray(image).save(os.path.join(root, img_path, frame_id + ".jpg"))
+    else:
+        with open(os.path.join(root, img_path, frame_id + ".jpg"), "wb") as fp:
+            fp.write(encoded)
     Tr = np.asarray(dest['Tr_ego2cam'])
     with open(os.path.join(root, "training", "calib", frame_id + ".txt"), "w") as fp:
         for key, val in (("P0", np.zeros((3, 4))), ("P1", np.zeros((3, 4))), ("P2", np.asarray(dest['P2'])), ("Tr_velo_to_cam", Tr[:3, :4])):
