@@ -1475,6 +1475,57 @@ int sgv3d_kitti_eval_device_host(int num_images, int total_gt, int total_dt, lon
                                  double *recall, double *orientation, int32_t *num_thresholds, int32_t *status,
                                  double *thresholds);
 
+/* ================================================================================================
+ * SAM's ViT image encoder (csrc/vit.hip): layers/backbones/sam_encoder.py of the reference, inference only.
+ * Every linear layer and convolution of the encoder runs through sgv3d_conv2d_forward; these five entries are the rest.
+ * Vector stores only, no float atomics: repeatable bit for bit.  f32 tensors; every tensor pointer 16-byte aligned.
+ * ================================================================================================ */
+
+/* Attention of one block.  Global attention is win_h = height, win_w = width; a window larger than the map is allowed. */
+typedef struct sgv3d_vit_attn_desc {
+    int batch, height, width; /* the token map [batch, height, width, ...]                                  */
+    int heads, head_dim;      /* head_dim 32, 64 or 80; heads * head_dim % 4 == 0                           */
+    int win_h, win_w;         /* window, 1..128 each; the map is padded up to a multiple of it on the fly   */
+} sgv3d_vit_attn_desc;
+
+/* Attention.forward between the qkv linear and the proj linear (sam_encoder.py:260-276) with window_partition /
+ * window_unpartition (:279-325) and add_decomposed_rel_pos (:361-397) folded in: ONE flash-style launch, online softmax,
+ * both products on v_mfma_f32_16x16x4_f32; no partitioned, padded or score tensor is written.
+ *   qkv        [batch, height, width, 3 * heads * head_dim], the qkv linear's output, last dimension ordered (3, heads, head_dim)
+ *   pad_qkv    [3 * heads * head_dim] or NULL: q, k, v of the tokens the window padding adds (h >= height or w >= width).
+ *              The reference pads the NORMED map with zeros before the qkv linear, so this is the qkv bias; NULL = zeros
+ *              (qkv_bias=False).  Such tokens are keys and values of their window; their output rows are not written.
+ *   rel_pos_h  [2 * win_h - 1, head_dim], rel_pos_w [2 * win_w - 1, head_dim]: the parameters as stored; both NULL = use_rel_pos=False
+ *   out        [batch, height, width, heads * head_dim]
+ * logit = (q * head_dim^-0.5) . k + q . rel_pos_h[qh - kh + win_h - 1] + q . rel_pos_w[qw - kw + win_w - 1] (the last two with
+ * the unscaled q).  Rejected by name (SGV3D_EINVAL) before any HIP call: another head_dim, heads * head_dim % 4 != 0, a zero
+ * dimension, a window above 128, one rel-pos table without the other, null or misaligned qkv / out. */
+int sgv3d_vit_attention(const sgv3d_vit_attn_desc *desc, const float *qkv, const float *pad_qkv, const float *rel_pos_h,
+                        const float *rel_pos_w, float *out, void *stream);
+
+/* nn.LayerNorm(C) over the last dimension of [rows, C] -- in NHWC also common.py's LayerNorm2d.  Two passes (the mean, then
+ * the variance of the residuals; never E[x^2] - E[x]^2) with the sums carried in f64, so that x - mean is rounded once,
+ * relative to itself, also for a row that sits far from zero.  C % 4 == 0; any row count.  y may be x. */
+int sgv3d_layernorm(long long rows, int channels, const float *x, const float *weight, const float *bias, float eps, float *y,
+                    void *stream);
+
+/* nn.GELU() (exact, erf form) of n values; y may be x. */
+int sgv3d_gelu(long long n, const float *x, float *y, void *stream);
+
+/* ImageEncoderViT.batch_preprocess (sam_encoder.py:124-139) into the layout the patch embedding reads.
+ *   img   [batch, 3, height, width], max(height, width) == size        mean, std  device f32 [3]
+ *   y     [batch, size, size, 4]: (img - mean) / std in channels 0..2, channel 3 zero; rows >= height and columns >= width
+ *         are ZERO (the padding follows the normalisation). */
+int sgv3d_vit_preprocess(int batch, int height, int width, const float *img, const float *mean, const float *std, int size,
+                         float *y, void *stream);
+
+/* ImageEncoderViT.postprocess (sam_encoder.py:117-122) on NHWC maps: x[:, :crop_h, :crop_w] (the crop clamped to the map),
+ * then F.interpolate(mode='bilinear', align_corners=False) to (out_h, out_w): source index max(0, (o + 0.5) * in / out - 0.5),
+ * upper neighbour clamped.  x [batch, h, w, channels], y [batch, out_h, out_w, channels], channels % 4 == 0.  Positions and
+ * the four-tap sum are evaluated in f64 and rounded once. */
+int sgv3d_resize_bilinear(int batch, int h, int w, int channels, int crop_h, int crop_w, int out_h, int out_w, const float *x,
+                          float *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

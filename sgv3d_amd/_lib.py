@@ -21,6 +21,11 @@ class ConvDesc(ctypes.Structure):
         "tile", "x_nchw", "k_order", "split_k")]
 
 
+class VitAttnDesc(ctypes.Structure):
+    """Mirror of ``sgv3d_vit_attn_desc`` (include/sgv3d_hip.h)."""
+    _fields_ = [(n, c_int) for n in ("batch", "height", "width", "heads", "head_dim", "win_h", "win_w")]
+
+
 CONV_NORMAL, CONV_DECONV, CONV_NCHW_OUT, CONV_GROUP_PLANES = 0, 1, 2, 3
 TILE_AUTO, TILE_128x128, TILE_128x64, TILE_64x128, TILE_64x64 = 0, 1, 2, 3, 4
 
@@ -249,6 +254,11 @@ _PROTOS = {
                                         c_void_p, c_size_t] + [c_void_p] * 6),
     "sgv3d_kitti_eval_device_host": (c_int, [c_int] * 3 + [c_ll, c_void_p, c_size_t, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                              c_int] + [c_void_p] * 6),
+    "sgv3d_vit_attention": (c_int, [ctypes.POINTER(VitAttnDesc)] + [c_void_p] * 6),
+    "sgv3d_layernorm": (c_int, [c_ll, c_int] + [c_void_p] * 3 + [ctypes.c_float, c_void_p, c_void_p]),
+    "sgv3d_gelu": (c_int, [c_ll, c_void_p, c_void_p, c_void_p]),
+    "sgv3d_vit_preprocess": (c_int, [c_int] * 3 + [c_void_p] * 3 + [c_int, c_void_p, c_void_p]),
+    "sgv3d_resize_bilinear": (c_int, [c_int] * 8 + [c_void_p] * 3),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)
