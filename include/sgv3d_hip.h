@@ -348,7 +348,11 @@ int sgv3d_conv_winograd4_pack_weight_x3(const float *w_src, int cout, int cin, i
  * (NORMAL mode, no gate; folded BN / bias, residual, ReLU, channel window and concat offsets; desc.split_k > 1 with a workspace of
  * sgv3d_conv2d_workspace_bytes(desc): partial sums, fixed-order reduce), desc.cout_pad = rows of
  * the x3 weights, desc.tile = SGV3D_TILE_X3 | variant [| SGV3D_TILE_MFIRST]: variant & 3 = {0: 32, 1: 64, 2: 128} output pixels
- * per workgroup, variant & 4: 64 instead of 128 channels. */
+ * per workgroup, variant & 4: 64 instead of 128 channels.
+ * DECONV mode (a kernel == stride transposed convolution, mmdet3d SECONDFPN's upsampling levels): desc as for sgv3d_conv2d_forward's
+ * DECONV (kh = kw = stride = 1, pad 0, deconv_ks >= 1, out = in * deconv_ks), no residual, cin % 32 == 0, cout % 4 == 0;
+ * u3_packed = sgv3d_conv_pack_weight_x3 of the [deconv_ks^2 * cout][cin][1][1] view of the weight with row = tap * cout + co, and
+ * desc.cout_pad = the rows of that pack.  Bit for bit the NORMAL launch over those columns followed by a pixel shuffle. */
 int sgv3d_conv_pack_weight_x3(const float *w_src, int cout, int cin, int kh, int kw, int cin_pad, int cout_pad, void *u3_packed,
                               void *stream);
 int sgv3d_conv2d_x3_forward(const sgv3d_conv_desc *desc, const float *x, const void *u3_packed, const float *scale,

@@ -64,9 +64,13 @@ struct PwX3Args {
 // y = act(t + (acc * scale2 + shift2)).  Every element's sums run in k-step order per source and the two epilogue expressions are
 // those of the two separate launches (shortcut first, then conv3 with that map as its residual): the output is theirs bit for bit.
 // No split-K.
+// MODE 4 (transposed convolution with kernel == stride == ks, SGV3D_CONV_DECONV: SECONDFPN's upsampling levels): the MODE 0 k-loop
+// with N = ks * ks * cout columns ordered column = tap * cout + co, and conv_epilogue_store's DECONV scatter in the epilogue: a
+// lane's 4 consecutive columns lie inside one tap (cout % 4 == 0), so it still moves 16 bytes per load and store.  The args carry
+// ks in `kh`, cout in `cin4` and the input / output map sizes in in_h, in_w / out_h, out_w (none of them read by the MODE 0 loop).
 template <int MA, int WN, int MODE>
 __global__ __launch_bounds__(64 * WN, 2) void conv_pw_x3_kernel(const PwX3Args a) {
-    constexpr bool TAPS = MODE == 1, TM = MODE == 2, DUAL = MODE == 3;
+    constexpr bool TAPS = MODE == 1, TM = MODE == 2, DUAL = MODE == 3, DECONV = MODE == 4;
     constexpr int NT = 64 * WN, BM = 16 * MA, BN = 32 * WN;
     constexpr int PLANE = BM * 64 + 64;
     constexpr int BUF = 3 * PLANE;
@@ -379,6 +383,29 @@ __global__ __launch_bounds__(64 * WN, 2) void conv_pw_x3_kernel(const PwX3Args a
         }
         return;
     }
+    if constexpr (DECONV) {
+        const int ks = a.kh, cout = a.cin4, hw = a.in_h * a.in_w;
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const int col = n0 + 32 * wave + 16 * nb + 4 * g;
+            if (col >= a.N) continue;
+            const int tap = (int)((unsigned)col / (unsigned)cout), co = col - tap * cout;
+            const int dy = (int)((unsigned)tap / (unsigned)ks), dx = tap - dy * ks;
+            const f32x4 sc = a.scale ? *reinterpret_cast<const f32x4 *>(a.scale + co) : f32x4{1.f, 1.f, 1.f, 1.f};
+            const f32x4 sh = a.bias ? *reinterpret_cast<const f32x4 *>(a.bias + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ma = 0; ma < MA; ++ma) {
+                const int row = m0 + 16 * ma + l16;
+                if (row >= a.M) continue;
+                const int img = (int)((unsigned)row / (unsigned)hw), pix = row - img * hw;
+                const int ih = (int)((unsigned)pix / (unsigned)a.in_w), iw = pix - ih * a.in_w;
+                f32x4 v = acc[ma][nb] * sc + sh;
+                v = f32x4{fmaxf(v[0], floor_), fmaxf(v[1], floor_), fmaxf(v[2], floor_), fmaxf(v[3], floor_)};
+                *reinterpret_cast<f32x4 *>(a.y + ((size_t)(img * a.out_h + ih * ks + dy) * a.out_w + (iw * ks + dx)) * a.y_ld + a.y_coff + co) = v;
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
         const int col = n0 + 32 * wave + 16 * nb + 4 * g;
@@ -430,7 +457,8 @@ __global__ __launch_bounds__(256) void pack_weight_x3_kernel(const float *__rest
 template <int MA, int WN>
 int launch_pw(const PwX3Args &a, int mode, hipStream_t st) {
     const dim3 grid(a.tiles_m * a.tiles_n, a.split_k > 1 ? a.split_k : 1);
-    if (mode == 3) hipLaunchKernelGGL((conv_pw_x3_kernel<MA, WN, 3>), grid, dim3(64 * WN), 0, st, a);
+    if (mode == 4) hipLaunchKernelGGL((conv_pw_x3_kernel<MA, WN, 4>), grid, dim3(64 * WN), 0, st, a);
+    else if (mode == 3) hipLaunchKernelGGL((conv_pw_x3_kernel<MA, WN, 3>), grid, dim3(64 * WN), 0, st, a);
     else if (mode == 2) hipLaunchKernelGGL((conv_pw_x3_kernel<MA, WN, 2>), grid, dim3(64 * WN), 0, st, a);
     else if (mode == 1) hipLaunchKernelGGL((conv_pw_x3_kernel<MA, WN, 1>), grid, dim3(64 * WN), 0, st, a);
     else hipLaunchKernelGGL((conv_pw_x3_kernel<MA, WN, 0>), grid, dim3(64 * WN), 0, st, a);
@@ -460,33 +488,47 @@ extern "C" int sgv3d_conv2d_x3_forward(const sgv3d_conv_desc *d, const float *x,
                                        void *stream) {
     SGV3D_REQUIRE(d && x && u3_packed && y, "conv2d_x3_forward: null pointer");
     const bool tapmajor = d->cin % 32 != 0;              // the weights' k order 0
-    SGV3D_REQUIRE(d->mode == SGV3D_CONV_NORMAL && d->kh > 0 && d->kw > 0 && d->kh * d->kw <= (tapmajor ? 64 : 32) && d->stride > 0 &&
+    const bool deconv = d->mode == SGV3D_CONV_DECONV;
+    if (deconv) {
+        // a 1x1 GEMM with ks * ks * cout columns (column = tap * cout + co, the rows of the packed weights) and a scatter epilogue
+        SGV3D_REQUIRE(d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 && d->deconv_ks >= 1 && d->deconv_ks <= 64 &&
+                          residual == nullptr,
+                      "conv2d_x3_forward: DECONV runs as a 1x1 GEMM with deconv_ks = kernel = stride (<= 64), no residual");
+        SGV3D_REQUIRE(d->in_h > 0 && d->in_w > 0 && d->out_h == d->in_h * d->deconv_ks && d->out_w == d->in_w * d->deconv_ks,
+                      "conv2d_x3_forward: DECONV output must be input * deconv_ks");
+        SGV3D_REQUIRE(d->cin > 0 && d->cin % 32 == 0 && d->cout > 0 && d->cout % 4 == 0 &&
+                          (long long)d->cout * d->deconv_ks * d->deconv_ks <= 0x1000000LL,
+                      "conv2d_x3_forward: DECONV needs cin %% 32 == 0, cout %% 4 == 0 (cin=%d cout=%d)", d->cin, d->cout);
+        SGV3D_REQUIRE((long long)d->batch * d->out_h * d->out_w < 0x7fffffffLL, "conv2d_x3_forward: DECONV output has 2^31 pixels or more");
+    }
+    SGV3D_REQUIRE((deconv || d->mode == SGV3D_CONV_NORMAL) && d->kh > 0 && d->kw > 0 && d->kh * d->kw <= (tapmajor ? 64 : 32) && d->stride > 0 &&
                       d->dil > 0 && d->pad >= 0,
                   "conv2d_x3_forward: NHWC output, at most 32 taps (64 with tap-major weights)");
     SGV3D_REQUIRE(d->batch > 0 && d->in_h > 0 && d->in_w > 0 && d->cin > 0 && d->cout > 0 && d->cin % 4 == 0 && d->cout % 4 == 0,
                   "conv2d_x3_forward: cin %% 4 == 0, cout %% 4 == 0 (cin=%d cout=%d)", d->cin, d->cout);
-    SGV3D_REQUIRE(d->out_h == (d->in_h + 2 * d->pad - d->dil * (d->kh - 1) - 1) / d->stride + 1 &&
-                      d->out_w == (d->in_w + 2 * d->pad - d->dil * (d->kw - 1) - 1) / d->stride + 1,
+    SGV3D_REQUIRE(deconv || (d->out_h == (d->in_h + 2 * d->pad - d->dil * (d->kh - 1) - 1) / d->stride + 1 &&
+                                 d->out_w == (d->in_w + 2 * d->pad - d->dil * (d->kw - 1) - 1) / d->stride + 1),
                   "conv2d_x3_forward: output size does not match the geometry");
     SGV3D_REQUIRE((d->x_ld & 3) == 0 && (d->x_coff & 3) == 0 && (d->y_ld & 3) == 0 && (d->y_coff & 3) == 0 && (residual == nullptr || (d->res_ld & 3) == 0),
                   "conv2d_x3_forward: leading dimensions and channel offsets must be multiples of 4");
     SGV3D_REQUIRE(d->x_ld >= d->x_coff + d->cin && d->y_ld >= d->y_coff + d->cout && (residual == nullptr || d->res_ld >= d->cout),
                   "conv2d_x3_forward: leading dimension too small");
-    SGV3D_REQUIRE(d->cout_pad >= d->cout && d->cout_pad % 32 == 0, "conv2d_x3_forward: desc.cout_pad = rows of the x3 weights (a multiple of 32)");
+    const int gemm_n = deconv ? d->cout * d->deconv_ks * d->deconv_ks : d->cout;
+    SGV3D_REQUIRE(d->cout_pad >= gemm_n && d->cout_pad % 32 == 0, "conv2d_x3_forward: desc.cout_pad = rows of the x3 weights (a multiple of 32)");
     SGV3D_REQUIRE(((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(residual) |
                     reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(u3_packed)) & 15) == 0,
                   "conv2d_x3_forward: pointers must be 16-B aligned");
-    const long long M = (long long)d->batch * d->out_h * d->out_w;
+    const long long M = deconv ? (long long)d->batch * d->in_h * d->in_w : (long long)d->batch * d->out_h * d->out_w;
     const long long K = tapmajor ? ((long long)d->kh * d->kw * d->cin + 31) / 32 * 32 : (long long)d->kh * d->kw * d->cin;
     const long long xb = (long long)d->batch * d->in_h * d->in_w * d->x_ld * 4, wb = (long long)d->cout_pad * K * 6;
     SGV3D_REQUIRE(M < 0x7fffffffLL && xb < 0xf0000000LL && wb < 0xf0000000LL, "conv2d_x3_forward: operands larger than 3.75 GiB");
     const int variant = d->tile & 15;
     SGV3D_REQUIRE((d->tile & SGV3D_TILE_X3) && (variant & 3) < 3 && (variant & 12) != 12,
                   "conv2d_x3_forward: desc.tile = SGV3D_TILE_X3 | variant, variant in {0,1,2, 4,5,6, 8,9,10}");
-    const int taps = tapmajor ? 2 : (d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0) ? 0 : 1;      // kernel MODE
+    const int taps = deconv ? 4 : tapmajor ? 2 : (d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0) ? 0 : 1;      // kernel MODE
     PwX3Args a;
     a.x = x; a.w = u3_packed; a.scale = scale; a.bias = bias; a.res = residual; a.y = y;
-    a.M = (int)M; a.K = (int)K; a.N = d->cout;
+    a.M = (int)M; a.K = (int)K; a.N = gemm_n;
     a.x_ld = d->x_ld; a.x_coff = d->x_coff; a.y_ld = d->y_ld; a.y_coff = d->y_coff; a.res_ld = d->res_ld; a.relu = d->relu;
     a.cout_pad = d->cout_pad;
     a.mfirst = (d->tile & SGV3D_TILE_MFIRST) ? 1 : 0;
@@ -494,15 +536,16 @@ extern "C" int sgv3d_conv2d_x3_forward(const sgv3d_conv_desc *d, const float *x,
     a.in_h = d->in_h; a.in_w = d->in_w; a.out_h = d->out_h; a.out_w = d->out_w;
     a.kh = d->kh; a.kw = d->kw; a.stride = d->stride; a.pad = d->pad; a.dil = d->dil;
     a.cin4 = d->cin / 4;
+    if (deconv) { a.kh = d->deconv_ks; a.cin4 = d->cout; }      // MODE 4: ks and the channels per tap
     const int bm = 32 << (variant & 3), bn = (variant & 8) ? 256 : (variant & 4) ? 64 : 128;
     a.tiles_m = (int)cdiv(M, bm);
-    a.tiles_n = cdiv(d->cout, bn);
+    a.tiles_n = cdiv(gemm_n, bn);
     hipStream_t st = as_stream(stream);
     a.split_k = d->split_k > 1 ? d->split_k : 1;
     a.ws = nullptr;
     if (a.split_k > 1) {
         SGV3D_REQUIRE(a.split_k <= K / 32, "conv2d_x3_forward: split_k %d exceeds the %lld k-steps", a.split_k, K / 32);
-        const size_t need = (size_t)a.split_k * (size_t)M * d->cout * sizeof(float);
+        const size_t need = (size_t)a.split_k * (size_t)M * gemm_n * sizeof(float);
         if (!workspace || workspace_bytes < need)
             return fail(SGV3D_ENOSPACE, "conv2d_x3_forward: split-K workspace has %zu bytes, needs %zu", workspace_bytes, need);
         SGV3D_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "conv2d_x3_forward: workspace must be 16-B aligned");
@@ -525,8 +568,8 @@ extern "C" int sgv3d_conv2d_x3_forward(const sgv3d_conv_desc *d, const float *x,
     ConvArgs r{};
     r.M = a.M; r.N = a.N; r.ws = a.ws; r.split_k = a.split_k;
     r.scale = scale; r.bias = bias; r.res = residual; r.res_ld = d->res_ld; r.relu = d->relu;
-    r.y = y; r.y_ld = d->y_ld; r.y_coff = d->y_coff; r.mode = SGV3D_CONV_NORMAL; r.cout = d->cout;
-    r.m_h = d->out_h; r.m_w = d->out_w; r.out_h = d->out_h; r.out_w = d->out_w;
+    r.y = y; r.y_ld = d->y_ld; r.y_coff = d->y_coff; r.mode = d->mode; r.ks = d->deconv_ks; r.cout = d->cout;
+    r.m_h = deconv ? d->in_h : d->out_h; r.m_w = deconv ? d->in_w : d->out_w; r.out_h = d->out_h; r.out_w = d->out_w;
     return launch_splitk_reduce(r, st);
 }
 

@@ -328,6 +328,18 @@ def _plan_w_pw_x3(pc, lib):
             (pc.cout, int(pc._keep.shape[1]), pc.kh, pc.kw, pc.cin, cout_pad), (), {"pw_x3_cout_pad": cout_pad})
 
 
+def _plan_w_pw_x3_deconv(pc, lib):
+    # transposed convolution (kernel == stride) on the f32x3 pointwise kernel: the x3 pack of the [ks * ks * cout][cin][1][1] view of
+    # the weight, row = tap * cout + co (the column order conv_epilogue_store's DECONV scatter decodes)
+    if not pc.transposed:
+        return None
+    n = pc.ks * pc.ks * pc.cout
+    w = pc._keep.permute(2, 3, 1, 0).reshape(n, int(pc._keep.shape[0]), 1, 1).contiguous()
+    cout_pad = _up32(n)
+    return (w, torch.empty(cout_pad // 16, pc.cin // 32, 3, 512, dtype=_BF16, device=w.device),
+            (n, int(w.shape[1]), 1, 1, pc.cin, cout_pad), (), {"pw_x3_deconv_cout_pad": cout_pad, "_keep_x3_deconv": w})
+
+
 def _plan_w_wino4_x3(pc, lib):
     # U[p] of F(4x4,3x3) as three bf16 planes per element: [36][cout_pad][cin / 32][3][32], cout_pad = cout rounded up to 32
     cout_pad = _up32(pc.cout)
@@ -362,6 +374,7 @@ _FORMS = {
     "w_wino4": _Form("w_wino4", "sgv3d_conv_winograd4_pack_weight", False, _plan_w_wino4),
     "w_pw_x3": _Form("w_pw_x3", "sgv3d_conv_pack_weight_x3", False, _plan_w_pw_x3),
     "w_wino4_x3": _Form("w_wino4_x3", "sgv3d_conv_winograd4_pack_weight_x3", False, _plan_w_wino4_x3),
+    "w_pw_x3_deconv": _Form("w_pw_x3_deconv", "sgv3d_conv_pack_weight_x3", False, _plan_w_pw_x3_deconv),
     # fragment-ordered bf16 weights of the direct-weight kernel / of the patch kernel
     "w_dw": _Form("w_dw", "sgv3d_conv_dw_bf16_pack_weight", True, _plan_w_dw),
     "w_patch": _Form("w_patch", "sgv3d_conv3x3_patch_bf16_pack_weight", True, lambda pc, lib: (
@@ -428,6 +441,7 @@ class PackedConv:
         # (the attributes of _FORMS, and what their packers note down for the launch)
         self._w = self._w_wino = self.w_bf16 = self.w_f4res = self.w_wino4 = self.w_pw_x3 = self.w_wino4_x3 = self.w_dw = self.w_patch = None
         self.wino4_geom = self.pw_x3_cout_pad = self.wino4_x3_cout_pad = self._keep_dw = None
+        self.w_pw_x3_deconv = self.pw_x3_deconv_cout_pad = self._keep_x3_deconv = None
         self._entry = None          # pack_cache._Entry when this object is kept across training steps (sgv3d_amd/pack_cache.py)
         self.device = device
         # Winograd F(2x2,3x3) covers the layer
@@ -1040,7 +1054,7 @@ def switch_state():
     return tuple(g.get(k) for k in ("AUTOTUNE", "SPLIT_K", "WINOGRAD", "FUSED_HEAD", "HEAD_PATH", "MFMA_BF16", "BF16_ACTIVATIONS",
                                     "MFMA_F32X3", "MFIRST", "WINO4", "WINO_HALF", "PATCH_BF16", "DW_BF16", "DW_DEEP", "DW_NARROW",
                                     "DW_SPLIT_K", "DW_DEEP_MAX_WGS", "PAIR_BF16", "TUNE_STREAMS", "PARALLEL_BRANCHES", "F4RES", "OCC5", "WINO4_G48", "DCN_FUSED", "WINO4_X3", "PW_X3",
-                                    "DCN_FUSED_BF16", "DCN_FUSED_TRAIN", "TRAIN_BF16_STORAGE", "SHORTCUT_X3"))
+                                    "DCN_FUSED_BF16", "DCN_FUSED_TRAIN", "TRAIN_BF16_STORAGE", "SHORTCUT_X3", "DECONV_X3"))
 
 
 def conv_pair_eligible(a, b, x, residual=None):
@@ -1229,6 +1243,145 @@ def conv_shortcut_choice(c3, ds, mid, x):
     TUNE_DB[sig] = [1, best] if on else [0, 0]
     _COMMITTED_SIGS.discard(sig)
     return best if on else 0
+
+# fp32 path: the kernel == stride transposed convolutions of the SECONDFPN necks on the f32x3 pointwise kernel (csrc/conv_pw_x3.hip
+# MODE 4: a 1x1 GEMM with ks * ks * cout columns and the transposed-conv scatter in its epilogue) instead of the f32 MFMA
+# implicit-GEMM kernel.  0 (SGV3D_DECONV_X3=0): always the layer's per-layer choice.
+DECONV_X3 = _os.environ.get("SGV3D_DECONV_X3", "1") != "0"
+
+
+def deconv_x3_eligible(conv, x, out=None, y_coff=0):
+    """``conv`` is a kernel == stride transposed convolution with cin % 32 == 0 and cout % 4 == 0 between f32 NHWC tensors, in the
+    fp32 mode with the f32x3 pointwise kernel enabled: the layers ``deconv_x3`` covers."""
+    if not (DECONV_X3 and PW_X3 and not MFMA_BF16 and not MFMA_F32X3):
+        return False
+    if not conv.transposed or conv.ks < 1 or conv.cin % 32 or conv.cout % 4 or x.dtype != torch.float32 or x.dim() != 4:
+        return False
+    x_ld = int(x.shape[-1])
+    if x_ld % 4 or x_ld < conv.cin or int(y_coff) % 4 or int(y_coff) < 0:
+        return False
+    if out is not None:
+        B, H, W, _ = (int(v) for v in x.shape)
+        return (out.dtype == torch.float32 and out.dim() == 4 and tuple(int(v) for v in out.shape[:3]) == (B,) + conv.out_hw(H, W)
+                and int(out.shape[-1]) % 4 == 0 and int(out.shape[-1]) >= int(y_coff) + conv.cout)
+    return True
+
+
+def _deconv_x3_rule(gemm_m, gemm_n):
+    """The fixed rule of ``deconv_x3``: (tile, split-K) = 128 channels per workgroup, the largest m-tile that still gives every CU two
+    workgroups, and no split-K -- what the per-layer fixed rule gives a NORMAL 1x1 layer of this GEMM size."""
+    return _shortcut_rule_tile(gemm_m, gemm_n), 1
+
+
+def _deconv_x3_candidates(gemm_m, gemm_n, nkt):
+    """The (tile, splits) pairs of ``deconv_x3`` worth timing: the pointwise kernel's shapes and split-K factors under the rules of
+    the per-layer candidate list for a NORMAL 1x1 layer of this GEMM size (m-tile first does not apply to the scatter)."""
+    pol = conv_tiles.SPLIT_POLICY["igemm"]
+    out = []
+    for t in PW_X3_TILES:
+        bm, bn = PW_X3_DIMS[t]
+        wgs = -(-gemm_m // bm) * -(-gemm_n // bn)
+        if TILES[t].mfirst or (bn == 256 and gemm_n < 256):
+            continue
+        if (wgs >= 96 or (SPLIT_K and nkt >= 16)) and (bn >= 128 or gemm_n <= 64 or wgs < 1024):
+            splits = (1,) + (tuple(s for s in conv_tiles.SPLITS if nkt // s >= pol["min_k"] and wgs < pol["max_wgs"]
+                                   and wgs * s <= pol["max_total"]) if SPLIT_K else ())
+            out.append((t, splits))
+    return tuple(out) or ((_shortcut_rule_tile(gemm_m, gemm_n), (1,)),)
+
+
+def deconv_x3(conv, x, out=None, y_coff=0, tile=None, split_k=None):
+    """The transposed convolution ``conv`` (kernel == stride, folded BN, ReLU) of ``x`` written to channels
+    [y_coff, y_coff + cout) of ``out``, on the f32x3 pointwise kernel.  ``tile``: a host id of the pw_x3 family, ``split_k``: the
+    split-K factor (default: the fixed rule's)."""
+    B, H, W, x_ld = (int(v) for v in x.shape)
+    oh, ow = conv.out_hw(H, W)
+    assert x.is_contiguous() and conv.transposed
+    if out is None:
+        out = torch.empty(B, oh, ow, conv.cout, dtype=torch.float32, device=x.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and tuple(int(v) for v in out.shape[:3]) == (B, oh, ow)
+    gemm_m, gemm_n = B * H * W, conv.ks * conv.ks * conv.cout
+    rule_t, rule_s = _deconv_x3_rule(gemm_m, gemm_n)
+    T = TILES[int(tile or rule_t)]
+    sk = int(split_k or rule_s)
+    if T.family != "pw_x3":
+        raise _lib.SGV3DError(f"deconv_x3: tile {T.id} is not a tile of the f32x3 pointwise kernel")
+    u = conv._form("w_pw_x3_deconv")
+    d = ConvDesc()
+    d.batch, d.in_h, d.in_w, d.cin = B, H, W, conv.cin
+    d.out_h, d.out_w, d.cout = oh, ow, conv.cout
+    d.kh, d.kw, d.stride, d.pad, d.dil = 1, 1, 1, 0, 1
+    d.x_ld, d.x_coff, d.y_ld, d.y_coff, d.res_ld = x_ld, 0, int(out.shape[-1]), int(y_coff), 0
+    d.relu, d.mode, d.deconv_ks, d.split_k, d.tile = (1 if conv.relu else 0), CONV_DECONV, conv.ks, sk, T.abi
+    d.k_pad, d.cout_pad, d.k_order = conv.cin, conv.pw_x3_deconv_cout_pad, 1
+    ws, nws = None, 0
+    if sk > 1:
+        nws = 4 * sk * gemm_m * gemm_n
+        ws = torch.empty(nws, dtype=torch.uint8, device=x.device)
+    real_n = conv.cout_real * conv.ks * conv.ks
+    flops = 2.0 * gemm_m * real_n * conv.cin_real
+    nbytes = 4.0 * (gemm_m * conv.cin_real + real_n * conv.cin_real + gemm_m * real_n)
+    name, extra = "conv_pw_x3_deconv", None
+    if PROFILE_DETAIL:
+        name += f"|{B}x{H}x{W}x{conv.cin}->{conv.cout} k{-conv.ks} s1 d1 splitk{sk}"
+    if PROFILE is not None:
+        mfma = 2.0 * gemm_m * gemm_n * conv.cin
+        extra = {"symbol": f"conv_pw_x3_kernel<{T.bm // 16}, {T.bn // 32}, 4>", "mfma_flops": mfma, "bf16_mfma_flops": 6 * mfma}
+    with torch.cuda.device(x.device), prof(name, flops, nbytes, extra):
+        rc = _lib.load().sgv3d_conv2d_x3_forward(ctypes.byref(d), x.data_ptr(), u.data_ptr(), _lib.ptr(conv.scale), _lib.ptr(conv.shift),
+                                                 None, out.data_ptr(), _lib.ptr(ws), nws, _st(x))
+    _lib.check(rc, "sgv3d_conv2d_x3_forward")
+    return out
+
+
+def deconv_x3_signature(conv, x):
+    B, H, W, _ = (int(v) for v in x.shape)
+    return f"pair|deconv|{conv.cout}x{conv.cin}ks{conv.ks}|{B}x{H}x{W}|r{int(conv.relu)}|ts{TUNE_STREAMS}"
+
+
+def deconv_x3_choice(conv, x, out=None, y_coff=0):
+    """(host tile id, split-K) to run ``deconv_x3`` with, or None when the layer's per-layer f32 choice is the faster way (or the
+    layer is not covered).  Measured once per layer and input shape under the load the pipeline runs -- the x3 launch with each of
+    its tiles and split-K factors against ``conv(x)`` -- and kept in the tune DB under a ``pair|deconv|`` signature as
+    [x3 or not, 100 * split-K + the x3 launch's tile] ([0, 0]: not).  The fixed rule (SGV3D_NO_AUTOTUNE, deterministic mode, a
+    capture that meets a new signature): x3, with ``_deconv_x3_rule``."""
+    if not deconv_x3_eligible(conv, x, out, y_coff):
+        return None
+    B, H, W, _ = (int(v) for v in x.shape)
+    gemm_m, gemm_n, nkt = B * H * W, conv.ks * conv.ks * conv.cout, conv.cin // 32
+    rule = _deconv_x3_rule(gemm_m, gemm_n)
+    if not AUTOTUNE:                                         # the documented fixed rule: no recorded measurement is consulted
+        return rule
+    sig = deconv_x3_signature(conv, x)
+    if sig in TUNE_DB and not (sig in _COMMITTED_SIGS and not _is_gfx950(x.device)):
+        on, code = (int(v) for v in TUNE_DB[sig])
+        if not on:
+            return None
+        sk, t = divmod(code, 100)
+        ok = t in PW_X3_TILES and not TILES[t].mfirst and 1 <= sk <= max(1, nkt) and (sk == 1 or SPLIT_K)
+        return (t, sk) if ok else rule
+    if deterministic() or torch.cuda.is_current_stream_capturing():
+        return rule
+    TUNE_STATS["measured"] += 1
+    if out is None:
+        out = torch.empty((B,) + conv.out_hw(H, W) + (conv.cout,), dtype=torch.float32, device=x.device)
+    old = lambda: conv(x, out, y_coff=y_coff)
+    old()
+    t2 = time_callable(old, x.device)
+    best, t1 = None, None
+    for t, splits in _deconv_x3_candidates(gemm_m, gemm_n, nkt):
+        for sk in splits:
+            one = lambda: deconv_x3(conv, x, out, y_coff, tile=t, split_k=sk)
+            one()
+            dt = time_callable(one, x.device)
+            if TUNE_VERBOSE:
+                print(f"[tune] {sig}: x3 tile {t} split {sk}: {dt * 1e3 / TUNE_ROUNDS:.1f} us (f32 choice {t2 * 1e3 / TUNE_ROUNDS:.1f} us)", flush=True)
+            if t1 is None or dt < t1:
+                best, t1 = (t, sk), dt
+    on = t1 < t2
+    TUNE_DB[sig] = [1, 100 * best[1] + best[0]] if on else [0, 0]
+    _COMMITTED_SIGS.discard(sig)
+    return best if on else None
 
 
 def time_callable(fn, device, rounds=None):

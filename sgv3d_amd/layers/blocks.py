@@ -380,7 +380,12 @@ class SECONDFPN(HipModule):
         for conv, f, oc in zip(convs, feats, self.out_channels):
             assert conv.out_hw(int(f.shape[1]), int(f.shape[2])) == (oh, ow), \
                 "SECONDFPN levels do not align (the reference's torch.cat would fail too)"
-            jobs.append(lambda conv=conv, f=f, off=off: conv(f, out, y_coff=off))
+            # fp32 mode: a transposed level on the f32x3 pointwise kernel where that measured faster (hip_ops.deconv_x3_choice)
+            x3 = hip_ops.deconv_x3_choice(conv, f, out, off) if out.dtype == torch.float32 else None
+            if x3 is not None:
+                jobs.append(lambda conv=conv, f=f, off=off, x3=x3: hip_ops.deconv_x3(conv, f, out, off, tile=x3[0], split_k=x3[1]))
+            else:
+                jobs.append(lambda conv=conv, f=f, off=off: conv(f, out, y_coff=off))
             off += oc
         # the levels are independent (each writes its own channel slice) and none of them fills the chip: side by side in the
         # captured graph (hip_ops.run_parallel), the largest level first
