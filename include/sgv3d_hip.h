@@ -1530,6 +1530,37 @@ int sgv3d_vit_preprocess(int batch, int height, int width, const float *img, con
 int sgv3d_resize_bilinear(int batch, int h, int w, int channels, int crop_h, int crop_w, int out_h, int out_w, const float *x,
                           float *y, void *stream);
 
+/* ================================================================================================
+ * The encoder's bf16 mode (csrc/vit_bf16.hip, hip_ops.VIT_BF16): between the two residual adds of a block every tensor is
+ * bf16 in HBM.  bf16 tensor pointers are void *.  Vector stores only, no atomics: repeatable bit for bit, graph-capturable.
+ * Every argument is checked on the host before any HIP call.
+ * ================================================================================================ */
+
+/* sgv3d_vit_attention on bf16 tensors: the same descriptor and semantics (padding tokens are pad_qkv, not zero; they are keys
+ * and values of their window; the relative-position terms use the unscaled q).
+ *   qkv        bf16 [batch, height, width, 3 * heads * head_dim], what the qkv layer writes with a bf16 output
+ *   pad_qkv, rel_pos_h, rel_pos_w   f32, the parameters as stored; rounded to bf16 (RNE) on the way in, so that a padding
+ *              token's q, k, v are what the bf16 qkv layer writes for a zero input
+ *   out        bf16 [batch, height, width, heads * head_dim]
+ * Both products run on v_mfma_f32_16x16x32_bf16 with f32 accumulation (head_dim 80 is zero-extended to 96 for Q K^T).
+ * head_dim^-0.5 multiplies the f32 accumulator; T_h = q R_h^T and T_w = q R_w^T are MFMA products with f32 sums, kept as f32
+ * and added to the f32 logit; the online softmax is f32.  P is rounded to bf16 once and the row sum adds the ROUNDED P, so the
+ * output is a convex combination of v with weights off by at most 2 * 2^-8 relatively; O / l is rounded to bf16 once.  Slots
+ * past win_h * win_w are masked (-inf) and their V is zero.
+ * Rejected by name (SGV3D_EINVAL): what sgv3d_vit_attention rejects, heads * head_dim % 8 != 0, and any of qkv, out, pad_qkv,
+ * rel_pos_h, rel_pos_w not 16-byte aligned. */
+int sgv3d_vit_attention_bf16(const sgv3d_vit_attn_desc *desc, const void *qkv, const float *pad_qkv, const float *rel_pos_h,
+                             const float *rel_pos_w, void *out, void *stream);
+
+/* sgv3d_layernorm with a bf16 result y [rows, channels]: the same arithmetic (two passes, sums in f64), rounded once more (RNE):
+ * bitwise sgv3d_layernorm followed by a cast.  channels % 8 == 0. */
+int sgv3d_layernorm_bf16out(long long rows, int channels, const float *x, const float *weight, const float *bias, float eps,
+                            void *y, void *stream);
+
+/* nn.GELU() on n bf16 values: sgv3d_gelu's f32 formulas (erf and erfc branches) on the widened value, rounded once (RNE): bitwise
+ * sgv3d_gelu on the widened input followed by a cast.  y may be x. */
+int sgv3d_gelu_bf16(long long n, const void *x, void *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

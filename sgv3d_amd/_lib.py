@@ -259,6 +259,9 @@ _PROTOS = {
     "sgv3d_gelu": (c_int, [c_ll, c_void_p, c_void_p, c_void_p]),
     "sgv3d_vit_preprocess": (c_int, [c_int] * 3 + [c_void_p] * 3 + [c_int, c_void_p, c_void_p]),
     "sgv3d_resize_bilinear": (c_int, [c_int] * 8 + [c_void_p] * 3),
+    "sgv3d_vit_attention_bf16": (c_int, [ctypes.POINTER(VitAttnDesc)] + [c_void_p] * 6),
+    "sgv3d_layernorm_bf16out": (c_int, [c_ll, c_int] + [c_void_p] * 3 + [ctypes.c_float, c_void_p, c_void_p]),
+    "sgv3d_gelu_bf16": (c_int, [c_ll, c_void_p, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

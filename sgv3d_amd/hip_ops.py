@@ -88,6 +88,10 @@ WGRAD_BF16_ALLTAPS = _os.environ.get("SGV3D_WGRAD_BF16_ALLTAPS", "1") != "0"
 # (csrc/conv_wgrad*.hip) and the io bits of PackedConv.  Takes effect only where train_bf16_storage_covers() says so; off, or not
 # covered: the f32 tensors of the MFMA_BF16 step, bit for bit.
 TRAIN_BF16_STORAGE = _os.environ.get("SGV3D_TRAIN_BF16_STORAGE", "0") not in ("", "0")
+# SAM ViT encoder in bf16 mode (SGV3D_VIT_BF16=1, default off): between the two residual adds of a Block every tensor is bf16 in HBM and
+# attention runs on the bf16 matrix cores (csrc/vit_bf16.hip); the residual stream, the patch embedding and the neck keep f32 tensors.
+# Takes effect only where vit_bf16_active() says so; off, or not covered: the f32-tensor path of the compute mode, bit for bit.
+VIT_BF16 = _os.environ.get("SGV3D_VIT_BF16", "0") not in ("", "0")
 # 1x1 layers with unpadded channel counts read the OIHW weight tensor itself as their packed weights (diagnostic: 0 packs a copy)
 ALIAS_1X1_WEIGHTS = _os.environ.get("SGV3D_ALIAS_1X1_WEIGHTS", "1") != "0"
 # True (SGV3D_F32X3=1): the implicit-GEMM layers compute float32-accurate products on the bf16 matrix cores -- every
@@ -270,6 +274,21 @@ def train_bf16_storage_covers(channel_counts):
         return False
     counts = [int(c) for c in channel_counts]
     return bool(counts) and all(c >= 16 and c % 8 == 0 for c in counts)
+
+
+def vit_bf16_covers(dim, num_heads, mlp_dim=None):
+    """Whether the bf16 kernels of the SAM ViT encoder take a Block of this shape: head_dim 32, 64 or 80 (sgv3d_vit_attention_bf16)
+    and 16-byte bf16 rows everywhere (dim and mlp_dim multiples of 8)."""
+    dim, num_heads = int(dim), int(num_heads)
+    if dim <= 0 or num_heads <= 0 or dim % num_heads or dim % 8:
+        return False
+    return dim // num_heads in (32, 64, 80) and (mlp_dim is None or (int(mlp_dim) > 0 and int(mlp_dim) % 8 == 0))
+
+
+def vit_bf16_active(dim, num_heads, mlp_dim=None):
+    """VIT_BF16 in bf16 compute mode (MFMA_BF16, not the f32x3 split) on a covered Block; otherwise the f32-tensor path runs,
+    silently, like the other coverage rules."""
+    return bool(VIT_BF16 and MFMA_BF16 and not MFMA_F32X3 and vit_bf16_covers(dim, num_heads, mlp_dim))
 
 
 def activation_dtype(*channel_counts):
@@ -1054,7 +1073,7 @@ def switch_state():
     return tuple(g.get(k) for k in ("AUTOTUNE", "SPLIT_K", "WINOGRAD", "FUSED_HEAD", "HEAD_PATH", "MFMA_BF16", "BF16_ACTIVATIONS",
                                     "MFMA_F32X3", "MFIRST", "WINO4", "WINO_HALF", "PATCH_BF16", "DW_BF16", "DW_DEEP", "DW_NARROW",
                                     "DW_SPLIT_K", "DW_DEEP_MAX_WGS", "PAIR_BF16", "TUNE_STREAMS", "PARALLEL_BRANCHES", "F4RES", "OCC5", "WINO4_G48", "DCN_FUSED", "WINO4_X3", "PW_X3",
-                                    "DCN_FUSED_BF16", "DCN_FUSED_TRAIN", "TRAIN_BF16_STORAGE", "SHORTCUT_X3", "DECONV_X3"))
+                                    "DCN_FUSED_BF16", "DCN_FUSED_TRAIN", "TRAIN_BF16_STORAGE", "SHORTCUT_X3", "DECONV_X3", "VIT_BF16"))
 
 
 def conv_pair_eligible(a, b, x, residual=None):

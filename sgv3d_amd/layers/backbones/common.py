@@ -13,8 +13,9 @@ from ... import _lib
 from ...hip_ops import PackedConv
 
 
-def require_device(x, what):
-    """The house rule: no CPU path and no autograd path -- both raise."""
+def require_device(x, what, bf16_ok=False):
+    """The house rule: no CPU path and no autograd path -- both raise.  ``bf16_ok``: the layer also takes the bf16 tensors of the
+    encoder's bf16 mode (hip_ops.VIT_BF16)."""
     if not isinstance(x, torch.Tensor):
         raise _lib.SGV3DError(f"{what}: a tensor is expected")
     if x.requires_grad and torch.is_grad_enabled():
@@ -22,31 +23,38 @@ def require_device(x, what):
                               "call it under torch.no_grad() or on a detached tensor")
     if not x.is_cuda:
         raise _lib.SGV3DError(f"{what}: the input must be a tensor on the GPU (there is no CPU fallback)")
-    if x.dtype != torch.float32:
+    if x.dtype != torch.float32 and not (bf16_ok and x.dtype == torch.bfloat16):
         raise _lib.SGV3DError(f"{what}: float32 input expected, got {x.dtype}")
 
 
-def layernorm(x, weight, bias, eps, out=None):
-    """LayerNorm over the last dimension of a contiguous f32 tensor (``nn.LayerNorm(C)``; on NHWC maps also ``LayerNorm2d``)."""
+def layernorm(x, weight, bias, eps, out=None, out_dtype=None):
+    """LayerNorm over the last dimension of a contiguous f32 tensor (``nn.LayerNorm(C)``; on NHWC maps also ``LayerNorm2d``).
+    ``out_dtype=torch.bfloat16`` (or a bf16 ``out``): the same f32 result rounded once to bf16 (sgv3d_layernorm_bf16out)."""
     assert x.is_contiguous() and x.dtype == torch.float32
     c = int(x.shape[-1])
     if out is None:
-        out = torch.empty_like(x)
+        out = torch.empty(x.shape, dtype=out_dtype or torch.float32, device=x.device)
+    assert out.is_contiguous() and out.shape == x.shape and out.dtype in (torch.float32, torch.bfloat16)
+    assert out_dtype is None or out.dtype == out_dtype
     lib = _lib.load()
+    bf16 = out.dtype == torch.bfloat16
+    fn, name = (lib.sgv3d_layernorm_bf16out, "sgv3d_layernorm_bf16out") if bf16 else (lib.sgv3d_layernorm, "sgv3d_layernorm")
     with torch.cuda.device(x.device):
-        rc = lib.sgv3d_layernorm(x.numel() // c, c, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), float(eps), out.data_ptr(),
-                                 _lib.stream_handle(x.device))
-    _lib.check(rc, "sgv3d_layernorm")
+        rc = fn(x.numel() // c, c, x.data_ptr(), weight.data_ptr(), bias.data_ptr(), float(eps), out.data_ptr(),
+                _lib.stream_handle(x.device))
+    _lib.check(rc, name)
     return out
 
 
 def gelu_(x):
-    """Exact (erf) GELU in place."""
-    assert x.is_contiguous() and x.dtype == torch.float32
+    """Exact (erf) GELU in place; on a bf16 tensor the f32 formula on the widened value, rounded once (sgv3d_gelu_bf16)."""
+    assert x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16)
     lib = _lib.load()
+    bf16 = x.dtype == torch.bfloat16
+    fn, name = (lib.sgv3d_gelu_bf16, "sgv3d_gelu_bf16") if bf16 else (lib.sgv3d_gelu, "sgv3d_gelu")
     with torch.cuda.device(x.device):
-        rc = lib.sgv3d_gelu(x.numel(), x.data_ptr(), x.data_ptr(), _lib.stream_handle(x.device))
-    _lib.check(rc, "sgv3d_gelu")
+        rc = fn(x.numel(), x.data_ptr(), x.data_ptr(), _lib.stream_handle(x.device))
+    _lib.check(rc, name)
     return x
 
 
@@ -80,10 +88,11 @@ class MLPBlock(nn.Module):
         self._p1, self._p2 = PackedParam(), PackedParam()
 
     def forward(self, x: torch.Tensor, residual=None) -> torch.Tensor:
-        """x [B, H, W, C] on the device -> lin2(gelu(lin1(x))) (+ ``residual``, added in lin2's epilogue)."""
-        require_device(x, "MLPBlock")
+        """x [B, H, W, C] on the device -> lin2(gelu(lin1(x))) (+ ``residual``, added in lin2's epilogue).  A bf16 ``x`` (the
+        encoder's bf16 mode): the hidden map stays bf16, lin2 writes f32."""
+        require_device(x, "MLPBlock", bf16_ok=True)
         with torch.no_grad():
-            h = self._p1.get(self.lin1.weight, self.lin1.bias)(x)
+            h = self._p1.get(self.lin1.weight, self.lin1.bias)(x, out_dtype=x.dtype)
             gelu_(h)
             return self._p2.get(self.lin2.weight, self.lin2.bias)(h, residual=residual)
 

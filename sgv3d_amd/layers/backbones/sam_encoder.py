@@ -14,6 +14,11 @@ Tokens are [B, H, W, C] as in the reference, which is this project's NHWC.  The 
 the attention kernel indexes the windows of the un-partitioned qkv map itself and takes the qkv BIAS as q, k, v of the
 padding tokens (the reference zero-pads the normed map before the qkv linear).  The relative-position tables must have
 the length 2 * size - 1 this constructor gives them; the reference's interpolation branch is not built.
+
+bf16 mode (hip_ops.VIT_BF16 with hip_ops.MFMA_BF16, on the shapes hip_ops.vit_bf16_covers names): between the two residual adds
+of a Block every tensor is bf16 in HBM -- sgv3d_layernorm_bf16out, qkv bf16 -> bf16, sgv3d_vit_attention_bf16, proj bf16 -> f32 +
+shortcut, sgv3d_layernorm_bf16out, lin1 bf16 -> bf16, sgv3d_gelu_bf16, lin2 bf16 -> f32 + shortcut: still eight launches.  The
+residual stream, the patch embedding, the neck, preprocess and resize keep f32 tensors.
 """
 import ctypes
 from functools import partial
@@ -22,7 +27,7 @@ from typing import List, Optional, Tuple, Type
 import torch
 from torch import nn
 
-from ... import _lib
+from ... import _lib, hip_ops
 from .common import LayerNorm2d, MLPBlock, PackedParam, layernorm, require_device
 
 
@@ -46,6 +51,32 @@ def vit_attention(qkv, num_heads, window, pad_qkv=None, rel_pos_h=None, rel_pos_
         rc = lib.sgv3d_vit_attention(ctypes.byref(d), qkv.data_ptr(), _lib.ptr(pad_qkv), _lib.ptr(rel_pos_h), _lib.ptr(rel_pos_w),
                                      out.data_ptr(), _lib.stream_handle(qkv.device))
     _lib.check(rc, "sgv3d_vit_attention")
+    return out
+
+
+def vit_attention_bf16(qkv, num_heads, window, pad_qkv=None, rel_pos_h=None, rel_pos_w=None, out=None):
+    """``vit_attention`` on bf16 tensors (sgv3d_vit_attention_bf16): qkv bf16 [B, H, W, 3 * C] -> bf16 [B, H, W, C].  ``pad_qkv`` and
+    the tables stay the f32 parameters; the kernel rounds them to bf16 on the way in."""
+    assert qkv.is_contiguous() and qkv.dtype == torch.bfloat16 and qkv.dim() == 4 and qkv.shape[-1] % (3 * num_heads) == 0
+    b, h, w, c3 = (int(s) for s in qkv.shape)
+    c = c3 // 3
+    d = _lib.VitAttnDesc(b, h, w, int(num_heads), c // int(num_heads), int(window[0]), int(window[1]))
+    for name, tab, win in (("rel_pos_h", rel_pos_h, d.win_h), ("rel_pos_w", rel_pos_w, d.win_w)):
+        if tab is not None and tuple(tab.shape) != (2 * win - 1, d.head_dim):
+            raise _lib.SGV3DError(f"{name} has shape {tuple(tab.shape)}, the window needs {(2 * win - 1, d.head_dim)}: "
+                                  "interpolated relative-position tables are not built")
+    for t in (pad_qkv, rel_pos_h, rel_pos_w):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
+    if pad_qkv is not None:
+        assert pad_qkv.numel() == c3
+    if out is None:
+        out = torch.empty(b, h, w, c, dtype=torch.bfloat16, device=qkv.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (b, h, w, c)
+    lib = _lib.load()
+    with torch.cuda.device(qkv.device):
+        rc = lib.sgv3d_vit_attention_bf16(ctypes.byref(d), qkv.data_ptr(), _lib.ptr(pad_qkv), _lib.ptr(rel_pos_h), _lib.ptr(rel_pos_w),
+                                          out.data_ptr(), _lib.stream_handle(qkv.device))
+    _lib.check(rc, "sgv3d_vit_attention_bf16")
     return out
 
 
@@ -200,12 +231,19 @@ class Block(nn.Module):
         self.mlp = MLPBlock(embedding_dim=dim, mlp_dim=int(dim * mlp_ratio), act=act_layer)
         self.window_size = window_size
 
+    def bf16_mode(self) -> bool:
+        """hip_ops.VIT_BF16 in bf16 compute mode on a covered shape: everything between the two residual adds is bf16 in HBM (the
+        LayerNorms write bf16, qkv / attention / lin1 / GELU read and write bf16, proj and lin2 read bf16, write f32 and add the
+        f32 residual).  The residual stream stays f32."""
+        return hip_ops.vit_bf16_active(self.attn.qkv.in_features, self.attn.num_heads, self.mlp.lin1.out_features)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         require_device(x, "Block")
         with torch.no_grad():
             window = (self.window_size, self.window_size) if self.window_size > 0 else None
-            x = self.attn(layernorm(x, *_norm_params(self.norm1)), window=window, residual=x)     # shortcut + attention
-            return self.mlp(layernorm(x, *_norm_params(self.norm2)), residual=x)                  # x + mlp(norm2(x))
+            act = torch.bfloat16 if self.bf16_mode() else None
+            x = self.attn(layernorm(x, *_norm_params(self.norm1), out_dtype=act), window=window, residual=x)     # shortcut + attention
+            return self.mlp(layernorm(x, *_norm_params(self.norm2), out_dtype=act), residual=x)                  # x + mlp(norm2(x))
 
 
 class Attention(nn.Module):
@@ -240,7 +278,8 @@ class Attention(nn.Module):
     def forward(self, x: torch.Tensor, window=None, residual=None) -> torch.Tensor:
         """x [B, H, W, C], the normed map, UN-partitioned.  ``window`` (win_h, win_w): attention inside the windows of the
         map padded up to whole windows, as window_partition / window_unpartition around this module give in the
-        reference; None: global.  ``residual`` is added in proj's epilogue."""
+        reference; None: global.  ``residual`` is added in proj's epilogue.  A bf16 ``x`` (the encoder's bf16 mode): qkv and the
+        attention output are bf16 tensors, proj writes f32."""
         _, h, w, _ = x.shape
         window = window or (int(h), int(w))
         if self.use_rel_pos:
@@ -248,12 +287,13 @@ class Attention(nn.Module):
                 if tab.shape[0] != 2 * win - 1:
                     raise _lib.SGV3DError(f"Attention: {name} has {tab.shape[0]} rows, a {window[0]} x {window[1]} window needs "
                                           f"{2 * win - 1}: interpolated relative-position tables are not built")
-        require_device(x, "Attention")
+        require_device(x, "Attention", bf16_ok=True)
         with torch.no_grad():
-            qkv = self._pqkv.get(self.qkv.weight, self.qkv.bias)(x)
+            qkv = self._pqkv.get(self.qkv.weight, self.qkv.bias)(x, out_dtype=x.dtype)
             rel = (self.rel_pos_h.detach(), self.rel_pos_w.detach()) if self.use_rel_pos else (None, None)
             bias = None if self.qkv.bias is None else self.qkv.bias.detach()
-            a = vit_attention(qkv, self.num_heads, window, bias, *rel)
+            attend = vit_attention_bf16 if x.dtype == torch.bfloat16 else vit_attention
+            a = attend(qkv, self.num_heads, window, bias, *rel)
             return self._pproj.get(self.proj.weight, self.proj.bias)(a, residual=residual)
 
 
