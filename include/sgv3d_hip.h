@@ -368,6 +368,17 @@ int sgv3d_conv2d_x3_forward(const sgv3d_conv_desc *desc, const float *x, const v
 int sgv3d_conv2d_x3_shortcut_forward(const sgv3d_conv_desc *desc_a, const float *xa, const void *u3a, const float *scale_a,
                                      const float *bias_a, const sgv3d_conv_desc *desc_b, const float *xb, const void *u3b,
                                      const float *scale_b, const float *bias_b, float *y, void *stream);
+/* The image stem in one launch (csrc/stem_pool_x3.hip): y = maxpool3x3 s2 p1(relu(scale * conv7x7 s2 p3(x) + shift)) -- mmdet ResNet's
+ * conv1 / bn1 / relu / maxpool (layers/backbones/lss_fpn.py:296-297) -- from the float32 NCHW image x_nchw [batch, 3, h, w] to the
+ * float32 NHWC map y_nhwc [batch, hp, wp, y_ld] (channels 0..63 written, the rest untouched), hc = (h - 1) / 2 + 1,
+ * hp = (hc - 1) / 2 + 1, likewise for w; any h, w >= 1.  64 output channels only.  w_x3: sgv3d_conv_pack_weight_x3 of the
+ * [64, 3, 7, 7] weight with cin_pad 4, cout_pad 64 (w_bytes >= 86016); scale / shift: the folded BN, 64 floats each, both null for
+ * scale 1 / shift 0.  variant: 0 (4 x 16 pooled pixels per workgroup).  The result equals, bit for bit, sgv3d_nchw_to_nhwc
+ * (c_pad 4), sgv3d_conv2d_x3_forward with that pack (ReLU, split_k 1, any tile) and sgv3d_maxpool3x3s2, without the two maps between
+ * them reaching memory.  Refuses (SGV3D_EINVAL) a null x / w / y, scale without shift, sizes <= 0, y_ld < 64 or y_ld % 4, an
+ * unknown variant, a short pack and weights / scale / shift / output that are not 16-B aligned. */
+int sgv3d_stem_pool_x3_forward(int batch, int h, int w, const float *x_nchw, const void *w_x3, size_t w_bytes, const float *scale,
+                               const float *shift, float *y_nhwc, int y_ld, int variant, void *stream);
 size_t sgv3d_conv2d_winograd4_workspace_bytes(const sgv3d_conv_desc *desc /*host*/);
 int sgv3d_conv2d_winograd4_forward(const sgv3d_conv_desc *desc /*host*/, const float *x, const float *u_packed,
                                    const float *scale, const float *bias, const float *residual, float *y,

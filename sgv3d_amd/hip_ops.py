@@ -1073,7 +1073,7 @@ def switch_state():
     return tuple(g.get(k) for k in ("AUTOTUNE", "SPLIT_K", "WINOGRAD", "FUSED_HEAD", "HEAD_PATH", "MFMA_BF16", "BF16_ACTIVATIONS",
                                     "MFMA_F32X3", "MFIRST", "WINO4", "WINO_HALF", "PATCH_BF16", "DW_BF16", "DW_DEEP", "DW_NARROW",
                                     "DW_SPLIT_K", "DW_DEEP_MAX_WGS", "PAIR_BF16", "TUNE_STREAMS", "PARALLEL_BRANCHES", "F4RES", "OCC5", "WINO4_G48", "DCN_FUSED", "WINO4_X3", "PW_X3",
-                                    "DCN_FUSED_BF16", "DCN_FUSED_TRAIN", "TRAIN_BF16_STORAGE", "SHORTCUT_X3", "DECONV_X3", "VIT_BF16"))
+                                    "DCN_FUSED_BF16", "DCN_FUSED_TRAIN", "TRAIN_BF16_STORAGE", "SHORTCUT_X3", "DECONV_X3", "VIT_BF16", "STEM_FUSED"))
 
 
 def conv_pair_eligible(a, b, x, residual=None):
@@ -1399,6 +1399,111 @@ def deconv_x3_choice(conv, x, out=None, y_coff=0):
                 best, t1 = (t, sk), dt
     on = t1 < t2
     TUNE_DB[sig] = [1, 100 * best[1] + best[0]] if on else [0, 0]
+    _COMMITTED_SIGS.discard(sig)
+    return best if on else None
+
+
+# fp32 path: the image stem -- NCHW ingest, 7x7 / stride 2 convolution with folded BN and ReLU, 3x3 / stride 2 max-pool -- as ONE launch
+# (csrc/stem_pool_x3.hip, sgv3d_stem_pool_x3_forward: f32x3 products, bit for bit the x3 tap-major convolution between the two small
+# kernels) instead of three; neither the 4-channel NHWC copy of the image nor the un-pooled map reaches memory.  0
+# (SGV3D_STEM_FUSED=0): always the three launches.
+STEM_FUSED = _os.environ.get("SGV3D_STEM_FUSED", "1") != "0"
+# variant code of sgv3d_stem_pool_x3_forward -> (pooled rows, pooled columns) per workgroup
+STEM_FUSED_VARIANTS = {0: (4, 16)}
+
+
+def stem_fused_eligible(conv, imgs, act_dtype=None, maxpool=True):
+    """``conv`` is a 7x7 / stride 2 / pad 3 layer from 3 image channels to 64 with folded BN and ReLU, followed by the 3x3 / stride 2 /
+    pad 1 max-pool (``maxpool``), applied to the contiguous f32 NCHW tensor ``imgs``, in the fp32 mode (``act_dtype``: the network's
+    activation dtype, None = f32 tensors) with the f32x3 pointwise kernel enabled: the stem ``stem_fused`` covers."""
+    if not (STEM_FUSED and PW_X3 and not MFMA_BF16 and not MFMA_F32X3) or act_dtype is not None or not maxpool:
+        return False
+    if conv.transposed or conv._entry is not None or not conv.relu or conv.scale is None or conv.shift is None:
+        return False
+    if (conv.kh, conv.kw, conv.stride, conv.pad, conv.dil) != (7, 7, 2, 3, 1) or (conv.cin_real, conv.cin, conv.cout_real, conv.cout) != (3, 4, 64, 64):
+        return False
+    return (torch.is_tensor(imgs) and imgs.dim() == 4 and int(imgs.shape[1]) == 3 and imgs.dtype == torch.float32 and imgs.is_contiguous()
+            and imgs.numel() > 0)
+
+
+def stem_fused_out_hw(h, w):
+    hc, wc = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+    return (hc - 1) // 2 + 1, (wc - 1) // 2 + 1
+
+
+def stem_fused(conv, imgs, out=None, variant=None):
+    """``maxpool3x3s2(conv(nchw_to_nhwc(imgs, c_pad=4)))`` in one launch, bit for bit what the three launches give with ``conv`` on the
+    f32x3 tap-major kernel (split-K 1).  ``variant``: a key of STEM_FUSED_VARIANTS (default 0)."""
+    B, C, H, W = (int(v) for v in imgs.shape)
+    assert C == 3 and imgs.is_contiguous() and imgs.dtype == torch.float32
+    variant = int(variant or 0)
+    if variant not in STEM_FUSED_VARIANTS:
+        raise _lib.SGV3DError(f"stem_fused: unknown variant {variant}")
+    hc, wc = conv.out_hw(H, W)
+    hp, wp = stem_fused_out_hw(H, W)
+    if out is None:
+        out = torch.empty(B, hp, wp, conv.cout, dtype=torch.float32, device=imgs.device)
+    assert out.is_contiguous() and out.dtype == torch.float32 and tuple(int(v) for v in out.shape[:3]) == (B, hp, wp)
+    u = conv._form("w_pw_x3")
+    flops = 2.0 * B * hc * wc * 64 * 147
+    nbytes = 4.0 * (B * 3 * H * W + 64 * 147 + B * hp * wp * 64)
+    name, extra = "conv_stem_fused", None
+    if PROFILE_DETAIL:
+        name += f"|{B}x{H}x{W}x3->64 k7 s2 + maxpool v{variant}"
+    if PROFILE is not None:
+        tph, tpw = STEM_FUSED_VARIANTS[variant]
+        # executed: per workgroup the (2 tph + 1) x (2 tpw + 1) conv pixels of its tile in groups of 16, two groups at a time on each
+        # half of the waves, x 64 channels x K = 224 (196 padded)
+        ng = -(-(2 * tph + 1) * (2 * tpw + 1) // 16)
+        groups = 2 * (-(-ng // 4) + -(-(ng - 1) // 4))
+        mfma = 2.0 * B * -(-hp // tph) * -(-wp // tpw) * groups * 16 * 64 * 224
+        extra = {"symbol": f"stem_pool_x3_kernel<{tph}, {tpw}>", "mfma_flops": mfma, "bf16_mfma_flops": 6 * mfma}
+    with torch.cuda.device(imgs.device), prof(name, flops, nbytes, extra):
+        rc = _lib.load().sgv3d_stem_pool_x3_forward(B, H, W, imgs.data_ptr(), u.data_ptr(), u.numel() * u.element_size(),
+                                                    _lib.ptr(conv.scale), _lib.ptr(conv.shift), out.data_ptr(), int(out.shape[-1]), variant,
+                                                    _st(imgs))
+    _lib.check(rc, "sgv3d_stem_pool_x3_forward")
+    return out
+
+
+def stem_fused_signature(conv, imgs):
+    B, _, H, W = (int(v) for v in imgs.shape)
+    return f"pair|stem|{conv.cout}x{conv.cin_real}k{conv.kh}|{B}x{H}x{W}|ts{TUNE_STREAMS}"
+
+
+def stem_fused_choice(conv, imgs, act_dtype=None, maxpool=True):
+    """The variant to run ``stem_fused`` with, or None when the three launches (``nchw_to_nhwc``, ``conv`` with its per-layer choice,
+    ``maxpool3x3s2``) are the faster way (or the stem is not covered).  Measured once per image shape under the load the pipeline runs
+    -- the fused launch with each of its variants against the three launches -- and kept in the tune DB under a ``pair|stem|``
+    signature as [fused or not, the fused launch's variant].  The fixed rule (SGV3D_NO_AUTOTUNE, deterministic mode, a capture that
+    meets a new signature): fused, variant 0."""
+    if not stem_fused_eligible(conv, imgs, act_dtype, maxpool):
+        return None
+    if not AUTOTUNE:                                         # the documented fixed rule: no recorded measurement is consulted
+        return 0
+    sig = stem_fused_signature(conv, imgs)
+    if sig in TUNE_DB and not (sig in _COMMITTED_SIGS and not _is_gfx950(imgs.device)):
+        on, v = (int(x) for x in TUNE_DB[sig])
+        if not on:
+            return None
+        return v if v in STEM_FUSED_VARIANTS else 0
+    if deterministic() or torch.cuda.is_current_stream_capturing():
+        return 0
+    TUNE_STATS["measured"] += 1
+    three = lambda: maxpool3x3s2(conv(nchw_to_nhwc(imgs, c_pad=conv.cin)))
+    three()
+    t3 = time_callable(three, imgs.device)
+    best, t1 = 0, None
+    for v in STEM_FUSED_VARIANTS:
+        one = lambda: stem_fused(conv, imgs, variant=v)
+        one()
+        dt = time_callable(one, imgs.device)
+        if TUNE_VERBOSE:
+            print(f"[tune] {sig}: fused variant {v}: {dt * 1e3 / TUNE_ROUNDS:.1f} us (three launches {t3 * 1e3 / TUNE_ROUNDS:.1f} us)", flush=True)
+        if t1 is None or dt < t1:
+            best, t1 = v, dt
+    on = t1 < t3
+    TUNE_DB[sig] = [1, best] if on else [0, 0]
     _COMMITTED_SIGS.discard(sig)
     return best if on else None
 

@@ -525,9 +525,7 @@ class LSSFPN(HipModule):
         """get_cam_feats (lss_fpn.py:403-414): [B,S,N,3,H,W] -> NHWC [B*S*N, fH, fW, 512]."""
         batch_size, num_sweeps, num_cams, num_channels, imH, imW = imgs.shape
         imgs = imgs.reshape(batch_size * num_sweeps * num_cams, num_channels, imH, imW).float().contiguous()
-        cin_pad = self.img_backbone.hip_state(imgs.device)['cin_pad']
-        x = hip_ops.nchw_to_nhwc(imgs, c_pad=cin_pad)
-        feats = self.img_backbone.hip_forward(x, split_tag="img_backbone.stage1")
+        feats = self.img_backbone.hip_forward_image(imgs, split_tag="img_backbone.stage1")
         # (bf16-activation mode: the concatenated neck map is a bf16 tensor too -- half the bytes, and HeightNet's first 3x3 gets the
         # bf16-in / bf16-out kernels)
         return self.img_neck.hip_forward(feats, out_dtype=hip_ops.activation_dtype(*self.img_neck.out_channels))

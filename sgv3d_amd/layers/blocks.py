@@ -302,6 +302,18 @@ class ResNet(HipModule):
         x = self.hip_state(x_nhwc.device)['stem'](x_nhwc, out_dtype=dt)
         if use_maxpool:
             x = hip_ops.maxpool3x3s2(x)
+        return self._hip_stages(x, dt, split_tag)
+
+    def hip_forward_image(self, imgs_nchw, split_tag=None):
+        """``hip_forward`` from the contiguous f32 NCHW image: ingest, stem and max-pool as one launch (hip_ops.stem_fused) where
+        ``hip_ops.stem_fused_choice`` says so, and exactly ``hip_forward(nchw_to_nhwc(imgs))`` otherwise."""
+        state = self.hip_state(imgs_nchw.device)
+        variant = hip_ops.stem_fused_choice(state['stem'], imgs_nchw, act_dtype=self.act_dtype())
+        if variant is None:
+            return self.hip_forward(hip_ops.nchw_to_nhwc(imgs_nchw, c_pad=state['cin_pad']), split_tag=split_tag)
+        return self._hip_stages(hip_ops.stem_fused(state['stem'], imgs_nchw, variant=variant), None, split_tag)
+
+    def _hip_stages(self, x, dt, split_tag):
         outs = []
         for i, name in enumerate(self.res_layers):
             for blk in getattr(self, name):
