@@ -94,8 +94,8 @@ def load_checkpoint(path, model, opt=None, *, strict=True, restore_rng=True):
     tune = extra.get('tune_db', {})
     if tune:
         from . import conv_grad
-        hip_ops.TUNE_DB.update({k: tuple(v) for k, v in tune.items()})
-        hip_ops._COMMITTED_SIGS.difference_update(tune)
+        for k, v in tune.items():
+            hip_ops.tune_record(k, tuple(v))                # (the run's own choices: no longer arch-bound)
         conv_grad._WGRAD_DB.clear()                 # (per-shape copies of TUNE_DB entries)
     opt_states = ckpt.get('optimizer_states') or []
     if opt is not None:

@@ -230,13 +230,12 @@ def _wgrad_choice(lib, d, x, dy, bf16=False):
         ws_bytes, launch = lib.sgv3d_conv2d_backward_weight_bf16_tensors_workspace_bytes, lib.sgv3d_conv2d_backward_weight_bf16_tensors
         alltaps_ws = lambda sp: lib.sgv3d_conv2d_backward_weight_bf16_alltaps_tensors_workspace_bytes(ctypes.byref(d), sp)
         alltaps = lib.sgv3d_conv2d_backward_weight_bf16_alltaps_tensors
-    if not hip_ops.AUTOTUNE:
-        return 0, 0                                          # the library's own rule, whatever a tune DB holds
-    if sig in hip_ops.TUNE_DB and not (sig in hip_ops._COMMITTED_SIGS and not hip_ops._is_gfx950(x.device)):
-        _WGRAD_DB[key] = tuple(hip_ops.TUNE_DB[sig])
+    hit = hip_ops.tune_lookup(sig, x.device)
+    if hit is not None:
+        _WGRAD_DB[key] = tuple(hit)
         return _WGRAD_DB[key]
-    if torch.cuda.is_current_stream_capturing() or hip_ops.deterministic():
-        return 0, 0
+    if not hip_ops.tune_may_measure():
+        return 0, 0                                          # the library's own rule (under SGV3D_NO_AUTOTUNE whatever a tune DB holds)
     pixels = d.batch * d.out_h * d.out_w
     cands = [(0, 0)]
     for t in ((1, 4) if bf16 else (1, 2, 3, 4)):
@@ -292,8 +291,7 @@ def _wgrad_choice(lib, d, x, dy, bf16=False):
                 best, best_t = (t, sp), dt
     d.tile = 0
     _WGRAD_DB[key] = best
-    hip_ops.TUNE_DB[sig] = list(best)
-    hip_ops._COMMITTED_SIGS.discard(sig)
+    hip_ops.tune_record(sig, list(best))
     return best
 
 

@@ -168,6 +168,47 @@ def _is_gfx950(device):
     return _ARCH_IS_GFX950[idx]
 
 
+# How every kernel that competes with another way of doing the same work is chosen, in this order: the fixed rule under
+# SGV3D_NO_AUTOTUNE; else the tune DB's entry (``tune_lookup``); else the fixed rule where nothing may be timed (``tune_may_measure``);
+# else the candidates are timed (``tune_best_of``, or the site's own loop) and the winner is written back (``tune_record``).  The sites:
+# PackedConv._call, conv_pair_choice, conv_shortcut_choice, deconv_x3_choice, stem_fused_choice, BEVHeightHead._branch_path and
+# conv_grad._wgrad_choice.
+def tune_lookup(sig, device):
+    """The tune DB's entry of ``sig`` as stored, or None: under SGV3D_NO_AUTOTUNE (the documented fixed rule consults no record), without
+    an entry, and for a committed ``tune/gfx950_*`` entry on a device that is not gfx950."""
+    if not AUTOTUNE or sig not in TUNE_DB or (sig in _COMMITTED_SIGS and not _is_gfx950(device)):
+        return None
+    return TUNE_DB[sig]
+
+
+def tune_may_measure():
+    """Candidates may be timed now: not under SGV3D_NO_AUTOTUNE, not inside a graph capture, not in deterministic mode."""
+    return AUTOTUNE and not deterministic() and not torch.cuda.is_current_stream_capturing()
+
+
+def tune_record(sig, entry):
+    """Keep ``entry`` as the choice of ``sig``: measured on THIS device (or restored from a run's own record), no longer arch-bound."""
+    TUNE_DB[sig] = entry
+    _COMMITTED_SIGS.discard(sig)
+
+
+def tune_best_of(sig, device, baseline, candidates):
+    """Time ``baseline`` and then each of ``candidates`` ((key, thunk) pairs, in their order) with ``time_callable``, each after one warming
+    call (a layer inside measures its own candidates there).  Returns (the baseline's time, the key of the fastest candidate -- the first
+    of equal ones --, its time); a candidate beats the baseline only when strictly faster, which the caller decides."""
+    baseline()
+    t0 = time_callable(baseline, device)
+    best, t1 = None, None
+    for key, fn in candidates:
+        fn()
+        dt = time_callable(fn, device)
+        if TUNE_VERBOSE:
+            print(f"[tune] {sig}: {key}: {dt * 1e3 / TUNE_ROUNDS:.1f} us (baseline {t0 * 1e3 / TUNE_ROUNDS:.1f} us)", flush=True)
+        if t1 is None or dt < t1:
+            best, t1 = key, dt
+    return t0, best, t1
+
+
 load_default_tune_dbs()
 load_tune_db()
 # Host tile ids: what every id means -- family, ABI code, workgroup footprint, weight form, split-K policy, profile symbol -- is ONE
@@ -188,6 +229,33 @@ WINO4_X3 = _os.environ.get("SGV3D_WINO4_X3", "1") != "0"
 PW_X3 = _os.environ.get("SGV3D_PW_X3", "1") != "0"
 PW_X3_TILES = conv_tiles.family("pw_x3")
 PW_X3_DIMS = {t: (TILES[t].bm, TILES[t].bn) for t in PW_X3_TILES}
+
+
+def _pw_x3_tiles(gemm_m, gemm_n, nkt=None, mfirst=True, skip=()):
+    """The pw_x3 tiles worth timing for a gemm_m x gemm_n GEMM, shapes that leave the chip neither empty nor padded: at least ~96
+    workgroups (or, where the launch can split K -- ``nkt``, its k-steps of 32, is given --, nkt >= 16), 64-channel tiles only for small
+    grids, 256-channel ones only where the GEMM has 256 columns, m-tile first only with several channel tiles (``mfirst`` False: never),
+    none of the (bm, bn) shapes in ``skip``."""
+    out = ()
+    for t in PW_X3_TILES:
+        bm, bn = PW_X3_DIMS[t]
+        wgs = -(-gemm_m // bm) * -(-gemm_n // bn)
+        if (bm, bn) in skip or (bn == 256 and gemm_n < 256) or (TILES[t].mfirst and not (mfirst and MFIRST and gemm_n > bn)):
+            continue
+        if (wgs >= 96 or (SPLIT_K and nkt is not None and nkt >= 16)) and (bn >= 128 or gemm_n <= 64 or wgs < 1024):
+            out += (t,)
+    return out
+
+
+def _split_factors(policy, nk, wgs):
+    """The split-K factors above 1 that a launch of ``wgs`` workgroups and ``nk`` k-steps may take under conv_tiles.SPLIT_POLICY[policy]
+    (none under SGV3D_NO_SPLITK)."""
+    if not SPLIT_K:
+        return ()
+    pol = conv_tiles.SPLIT_POLICY[policy]
+    return tuple(s for s in conv_tiles.SPLITS if nk // s >= pol["min_k"] and wgs < pol["max_wgs"] and wgs * s <= pol["max_total"])
+
+
 # F(4x4,3x3) in ONE launch (TILE_F4RES): 3x3 / stride 1 / pad 1 layers with 64 input channels (ResNet layer 1) or 64 output channels
 # (the CenterHead's shared layer), f32
 F4RES = _os.environ.get("SGV3D_F4RES", "1") != "0"     # 0: never a candidate
@@ -636,12 +704,11 @@ class PackedConv:
                 if choice is not None:
                     self._tile_cache[key] = choice
                     TUNE_STATS["from_db"] += 1
-                elif AUTOTUNE and not torch.cuda.is_current_stream_capturing() and not deterministic():
+                elif tune_may_measure():
                     TUNE_STATS["measured"] += 1
                     choice = self._autotune(lib, d, x, residual, gate, out, gemm_m, gemm_n, nkt, t, sk, io)
                     self._tile_cache[key] = choice
-                    TUNE_DB[sig] = choice
-                    _COMMITTED_SIGS.discard(sig)        # measured on THIS device
+                    tune_record(sig, choice)
                 else:
                     choice = self._rule(t, sk, d, gemm_m, gemm_n, gate)
             t, sk = choice
@@ -866,14 +933,7 @@ class PackedConv:
         if self.f4res_ok(d, gate, io):
             tiles += (TILE_F4RES,)
         if self.pw_x3_ok(d, gate, io):
-            # shapes that leave the chip neither empty nor padded: at least ~128 workgroups, m-tiles no larger than the map needs
-            for t in PW_X3_TILES:
-                bm, bn = PW_X3_DIMS[t]
-                wgs = -(-gemm_m // bm) * -(-gemm_n // bn)
-                if bn == 256 and gemm_n < 256:
-                    continue
-                if (wgs >= 96 or (SPLIT_K and nkt >= 16)) and (bn >= 128 or gemm_n <= 64 or wgs < 1024) and (not TILES[t].mfirst or (MFIRST and gemm_n > bn)):
-                    tiles += (t,)
+            tiles += _pw_x3_tiles(gemm_m, gemm_n, nkt)
         if self._patch_eligible(d, gate):
             tiles += (TILE_PATCH,)
         if self._dw_eligible(d, gate, io):
@@ -905,12 +965,9 @@ class PackedConv:
                 splits = (1,)
             elif fixed_split:
                 splits = (fixed_split,)
-            elif not SPLIT_K:
-                splits = (1,)
             else:
-                pol = conv_tiles.SPLIT_POLICY[T.split]
-                splits = [1] + [s for s in conv_tiles.SPLITS if nk // s >= pol["min_k"] and wgs < pol["max_wgs"] and wgs * s <= pol["max_total"]]
-            cands.append((t, tuple(splits)))
+                splits = (1,) + _split_factors(T.split, nk, wgs)
+            cands.append((t, splits))
         return cands
 
     def _x3_tiles(self, d):
@@ -932,12 +989,8 @@ class PackedConv:
         input / output layout the recorded kernel does not cover (channel offsets / strides are not part of the
         signature) and SGV3D_NO_AUTOTUNE (the documented fixed rule) all win over it, and the committed ``tune/gfx950_*``
         entries only apply on a gfx950 device."""
-        if not AUTOTUNE:
-            return None
-        choice = TUNE_DB.get(sig)
+        choice = tune_lookup(sig, x.device)
         if choice is None:
-            return None
-        if sig in _COMMITTED_SIGS and not _is_gfx950(x.device):
             return None
         t, sk = int(choice[0]), int(choice[1])
         for ct, splits in self._candidates(d, gate, gemm_m, gemm_n, nkt, fixed_tile, fixed_split, io):
@@ -1116,20 +1169,18 @@ def conv_pair_choice(a, b, x, residual=None):
         return False
     B, H, W, _ = (int(v) for v in x.shape)
     sig = (f"pair|{a.cout}x{a.cin}k{a.kh}x{a.kw}s{a.stride}p{a.pad}d{a.dil}->{b.cout}|{B}x{H}x{W}|r{int(residual is not None)}|bf16|ts{TUNE_STREAMS}")
-    if not AUTOTUNE:                                         # the documented fixed rule: no recorded measurement is consulted
-        return True
-    if sig in TUNE_DB and not (sig in _COMMITTED_SIGS and not _is_gfx950(x.device)):
-        return bool(TUNE_DB[sig][0])
-    if torch.cuda.is_current_stream_capturing() or deterministic():
+    hit = tune_lookup(sig, x.device)
+    if hit is not None:
+        return bool(hit[0])
+    if not tune_may_measure():                               # the fixed rule: fused
         return True
     act = torch.bfloat16
     two = lambda: b(a(x, out_dtype=act), residual=residual, out_dtype=act)
     one = lambda: conv_pair_bf16(a, b, x, residual)
-    two(); one()
+    two(); one()                                             # (both sides warm before either is timed: not tune_best_of's order)
     t2 = time_callable(two, x.device)
     t1 = time_callable(one, x.device)
-    TUNE_DB[sig] = [1 if t1 < t2 else 0, 0]
-    _COMMITTED_SIGS.discard(sig)
+    tune_record(sig, [1 if t1 < t2 else 0, 0])
     return t1 < t2
 
 
@@ -1166,18 +1217,9 @@ def _shortcut_rule_tile(gemm_m, gemm_n):
 
 
 def _shortcut_tiles(gemm_m, gemm_n):
-    """The tiles of the two-source launch worth timing: the pointwise kernel's shapes under the rules of the per-layer candidate
-    list (at least ~96 workgroups, 64-channel tiles only for small grids, 256-channel ones only where cout has them, m-tile first only
-    with several channel tiles) -- without 128 x 64, the one instantiation of the two-source form that spills registers."""
-    out = []
-    for t in PW_X3_TILES:
-        bm, bn = PW_X3_DIMS[t]
-        wgs = -(-gemm_m // bm) * -(-gemm_n // bn)
-        if (bm, bn) == (128, 64) or (bn == 256 and gemm_n < 256) or wgs < 96:
-            continue
-        if (bn >= 128 or gemm_n <= 64 or wgs < 1024) and (not TILES[t].mfirst or (MFIRST and gemm_n > bn)):
-            out.append(t)
-    return tuple(out) or (_shortcut_rule_tile(gemm_m, gemm_n),)
+    """The tiles of the two-source launch worth timing: the per-layer candidate list's (``_pw_x3_tiles``) for a launch that cannot split
+    K -- without 128 x 64, the one instantiation of the two-source form that spills registers."""
+    return _pw_x3_tiles(gemm_m, gemm_n, skip=((128, 64),)) or (_shortcut_rule_tile(gemm_m, gemm_n),)
 
 
 def conv_shortcut_x3(c3, ds, mid, x, out=None, tile=None):
@@ -1234,33 +1276,21 @@ def conv_shortcut_choice(c3, ds, mid, x):
         return 0
     gemm_m, gemm_n = int(mid.shape[0]) * int(mid.shape[1]) * int(mid.shape[2]), c3.cout
     rule = _shortcut_rule_tile(gemm_m, gemm_n)
-    if not AUTOTUNE:                                         # the documented fixed rule: no recorded measurement is consulted
-        return rule
     sig = conv_shortcut_signature(c3, ds, x)
-    if sig in TUNE_DB and not (sig in _COMMITTED_SIGS and not _is_gfx950(x.device)):
-        on, t = (int(v) for v in TUNE_DB[sig])
+    hit = tune_lookup(sig, x.device)
+    if hit is not None:
+        on, t = (int(v) for v in hit)
         if not on:
             return 0
         return t if t in PW_X3_TILES else rule
-    if torch.cuda.is_current_stream_capturing() or deterministic():
+    if not tune_may_measure():
         return rule
     TUNE_STATS["measured"] += 1
     out = torch.empty(tuple(mid.shape[:3]) + (c3.cout,), dtype=torch.float32, device=x.device)
-    two = lambda: c3(mid, out, residual=ds(x))
-    two()
-    t2 = time_callable(two, x.device)
-    best, t1 = 0, None
-    for t in _shortcut_tiles(gemm_m, gemm_n):
-        one = lambda: conv_shortcut_x3(c3, ds, mid, x, out, tile=t)
-        one()
-        dt = time_callable(one, x.device)
-        if TUNE_VERBOSE:
-            print(f"[tune] {sig}: fused tile {t}: {dt * 1e3 / TUNE_ROUNDS:.1f} us (two launches {t2 * 1e3 / TUNE_ROUNDS:.1f} us)", flush=True)
-        if t1 is None or dt < t1:
-            best, t1 = t, dt
+    t2, best, t1 = tune_best_of(sig, x.device, lambda: c3(mid, out, residual=ds(x)),
+                                [(t, lambda t=t: conv_shortcut_x3(c3, ds, mid, x, out, tile=t)) for t in _shortcut_tiles(gemm_m, gemm_n)])
     on = t1 < t2
-    TUNE_DB[sig] = [1, best] if on else [0, 0]
-    _COMMITTED_SIGS.discard(sig)
+    tune_record(sig, [1, best] if on else [0, 0])
     return best if on else 0
 
 # fp32 path: the kernel == stride transposed convolutions of the SECONDFPN necks on the f32x3 pointwise kernel (csrc/conv_pw_x3.hip
@@ -1293,20 +1323,11 @@ def _deconv_x3_rule(gemm_m, gemm_n):
 
 
 def _deconv_x3_candidates(gemm_m, gemm_n, nkt):
-    """The (tile, splits) pairs of ``deconv_x3`` worth timing: the pointwise kernel's shapes and split-K factors under the rules of
-    the per-layer candidate list for a NORMAL 1x1 layer of this GEMM size (m-tile first does not apply to the scatter)."""
-    pol = conv_tiles.SPLIT_POLICY["igemm"]
-    out = []
-    for t in PW_X3_TILES:
-        bm, bn = PW_X3_DIMS[t]
-        wgs = -(-gemm_m // bm) * -(-gemm_n // bn)
-        if TILES[t].mfirst or (bn == 256 and gemm_n < 256):
-            continue
-        if (wgs >= 96 or (SPLIT_K and nkt >= 16)) and (bn >= 128 or gemm_n <= 64 or wgs < 1024):
-            splits = (1,) + (tuple(s for s in conv_tiles.SPLITS if nkt // s >= pol["min_k"] and wgs < pol["max_wgs"]
-                                   and wgs * s <= pol["max_total"]) if SPLIT_K else ())
-            out.append((t, splits))
-    return tuple(out) or ((_shortcut_rule_tile(gemm_m, gemm_n), (1,)),)
+    """The (tile, splits) pairs of ``deconv_x3`` worth timing: the per-layer candidate list's tiles (``_pw_x3_tiles``) and split-K factors
+    (``_split_factors``) for a NORMAL 1x1 layer of this GEMM size (m-tile first does not apply to the scatter)."""
+    wgs = lambda t: -(-gemm_m // TILES[t].bm) * -(-gemm_n // TILES[t].bn)
+    out = tuple((t, (1,) + _split_factors("igemm", nkt, wgs(t))) for t in _pw_x3_tiles(gemm_m, gemm_n, nkt, mfirst=False))
+    return out or ((_shortcut_rule_tile(gemm_m, gemm_n), (1,)),)
 
 
 def deconv_x3(conv, x, out=None, y_coff=0, tile=None, split_k=None):
@@ -1369,37 +1390,25 @@ def deconv_x3_choice(conv, x, out=None, y_coff=0):
     B, H, W, _ = (int(v) for v in x.shape)
     gemm_m, gemm_n, nkt = B * H * W, conv.ks * conv.ks * conv.cout, conv.cin // 32
     rule = _deconv_x3_rule(gemm_m, gemm_n)
-    if not AUTOTUNE:                                         # the documented fixed rule: no recorded measurement is consulted
-        return rule
     sig = deconv_x3_signature(conv, x)
-    if sig in TUNE_DB and not (sig in _COMMITTED_SIGS and not _is_gfx950(x.device)):
-        on, code = (int(v) for v in TUNE_DB[sig])
+    hit = tune_lookup(sig, x.device)
+    if hit is not None:
+        on, code = (int(v) for v in hit)
         if not on:
             return None
         sk, t = divmod(code, 100)
         ok = t in PW_X3_TILES and not TILES[t].mfirst and 1 <= sk <= max(1, nkt) and (sk == 1 or SPLIT_K)
         return (t, sk) if ok else rule
-    if deterministic() or torch.cuda.is_current_stream_capturing():
+    if not tune_may_measure():
         return rule
     TUNE_STATS["measured"] += 1
     if out is None:
         out = torch.empty((B,) + conv.out_hw(H, W) + (conv.cout,), dtype=torch.float32, device=x.device)
-    old = lambda: conv(x, out, y_coff=y_coff)
-    old()
-    t2 = time_callable(old, x.device)
-    best, t1 = None, None
-    for t, splits in _deconv_x3_candidates(gemm_m, gemm_n, nkt):
-        for sk in splits:
-            one = lambda: deconv_x3(conv, x, out, y_coff, tile=t, split_k=sk)
-            one()
-            dt = time_callable(one, x.device)
-            if TUNE_VERBOSE:
-                print(f"[tune] {sig}: x3 tile {t} split {sk}: {dt * 1e3 / TUNE_ROUNDS:.1f} us (f32 choice {t2 * 1e3 / TUNE_ROUNDS:.1f} us)", flush=True)
-            if t1 is None or dt < t1:
-                best, t1 = (t, sk), dt
+    t2, best, t1 = tune_best_of(sig, x.device, lambda: conv(x, out, y_coff=y_coff),
+                                [((t, sk), lambda t=t, sk=sk: deconv_x3(conv, x, out, y_coff, tile=t, split_k=sk))
+                                 for t, splits in _deconv_x3_candidates(gemm_m, gemm_n, nkt) for sk in splits])
     on = t1 < t2
-    TUNE_DB[sig] = [1, 100 * best[1] + best[0]] if on else [0, 0]
-    _COMMITTED_SIGS.discard(sig)
+    tune_record(sig, [1, 100 * best[1] + best[0]] if on else [0, 0])
     return best if on else None
 
 
@@ -1479,32 +1488,20 @@ def stem_fused_choice(conv, imgs, act_dtype=None, maxpool=True):
     meets a new signature): fused, variant 0."""
     if not stem_fused_eligible(conv, imgs, act_dtype, maxpool):
         return None
-    if not AUTOTUNE:                                         # the documented fixed rule: no recorded measurement is consulted
-        return 0
     sig = stem_fused_signature(conv, imgs)
-    if sig in TUNE_DB and not (sig in _COMMITTED_SIGS and not _is_gfx950(imgs.device)):
-        on, v = (int(x) for x in TUNE_DB[sig])
+    hit = tune_lookup(sig, imgs.device)
+    if hit is not None:
+        on, v = (int(x) for x in hit)
         if not on:
             return None
         return v if v in STEM_FUSED_VARIANTS else 0
-    if deterministic() or torch.cuda.is_current_stream_capturing():
+    if not tune_may_measure():
         return 0
     TUNE_STATS["measured"] += 1
-    three = lambda: maxpool3x3s2(conv(nchw_to_nhwc(imgs, c_pad=conv.cin)))
-    three()
-    t3 = time_callable(three, imgs.device)
-    best, t1 = 0, None
-    for v in STEM_FUSED_VARIANTS:
-        one = lambda: stem_fused(conv, imgs, variant=v)
-        one()
-        dt = time_callable(one, imgs.device)
-        if TUNE_VERBOSE:
-            print(f"[tune] {sig}: fused variant {v}: {dt * 1e3 / TUNE_ROUNDS:.1f} us (three launches {t3 * 1e3 / TUNE_ROUNDS:.1f} us)", flush=True)
-        if t1 is None or dt < t1:
-            best, t1 = v, dt
+    t3, best, t1 = tune_best_of(sig, imgs.device, lambda: maxpool3x3s2(conv(nchw_to_nhwc(imgs, c_pad=conv.cin))),
+                                [(v, lambda v=v: stem_fused(conv, imgs, variant=v)) for v in STEM_FUSED_VARIANTS])
     on = t1 < t3
-    TUNE_DB[sig] = [1, best] if on else [0, 0]
-    _COMMITTED_SIGS.discard(sig)
+    tune_record(sig, [1, best] if on else [0, 0])
     return best if on else None
 
 

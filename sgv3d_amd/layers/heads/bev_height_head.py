@@ -235,10 +235,10 @@ class BEVHeightHead(HipModule):
         B, H, W, _ = (int(v) for v in shared.shape)
         sig = f"centerhead_branches3|{B}x{H}x{W}x{s['nb']}|ts{hip_ops.TUNE_STREAMS}"
         ok = {0: True, 1: s['first'].wino4_ok(), 2: f4_ok}
-        hit = hip_ops.TUNE_DB.get(sig) if hip_ops.AUTOTUNE else None
+        hit = hip_ops.tune_lookup(sig, shared.device)
         if hit is not None and ok.get(int(hit[0]) - 100, False):
             return int(hit[0]) - 100
-        if not hip_ops.AUTOTUNE or torch.cuda.is_current_stream_capturing() or hip_ops.deterministic():
+        if not hip_ops.tune_may_measure():
             return 2 if f4_ok else 0
         cands = {0: lambda: hip_ops.centerhead_branches(shared, s['first'], s['w2'], s['b2'], s['out_begin'], s['nb']),
                  1: lambda: self._two_kernel_branches(s, shared), 2: lambda: self._fused_f4(s, shared)}
@@ -248,7 +248,7 @@ class BEVHeightHead(HipModule):
         torch.cuda.synchronize(shared.device)
         times = {k: hip_ops.time_callable(f, shared.device, rounds=2) for k, f in cands.items()}
         choice = min(times, key=times.get)
-        hip_ops.TUNE_DB[sig] = (100 + choice, 1)
+        hip_ops.tune_record(sig, (100 + choice, 1))
         return choice
 
     def forward(self, x, nhwc=False):
