@@ -576,7 +576,8 @@ int sgv3d_head_final_conv(int batch, int h, int w, int num_branches, int hidden_
  *   w1_wino   first-layer weights of all branches, [num_branches*64, cin, 3, 3] packed by
  *             sgv3d_conv_winograd_pack_weight; scale1 / bias1 f32 [num_branches*64] folded BN (NULL = 1 / 0)
  *   w2        f32 [total_out][3][3][64], bias2 f32 [total_out]; out_begin int32 [num_branches + 1] (device):
- *             branch k owns output channels [out_begin[k], out_begin[k+1]), at most 4
+ *             branch k owns output channels [out_begin[k], out_begin[k+1]): any number (the model's branches have at
+ *             most 4; outputs from the fifth on take a slower pass, four at a time)
  *   out       f32 NCHW [batch, total_out, h, w]
  *   workspace sgv3d_centerhead_branches_workspace_bytes(...) bytes of scratch (ring partial sums) */
 size_t sgv3d_centerhead_branches_workspace_bytes(int batch, int h, int w, int total_out);

@@ -856,12 +856,16 @@ __global__ __launch_bounds__(256, 1) void conv_wino_resident_kernel(const ConvAr
 // LDS (160 KB): patch of all k-steps without pad slots (8 x 648 x 16 B = 81 KB; costs a 2-way conflict on a
 // quarter of the patch reads), hidden tile [256 px + 1 zero px][68 floats] (17 16-B slots per pixel:
 // conflict-free for thread = pixel), final weights of the branch [c][9 taps][64] (<= 9 KB).
+//
+// A branch has any number of outputs.  The first HEAD_MAX_OUT of them (every branch of the model: at most 4) take the path
+// above; a wider branch runs its further outputs first, HEAD_MAX_OUT per pass with thread = pixel over all 64 channels,
+// because the channel-split own-pixel phase ends with its partial sums over the hidden tile.
 constexpr int HID_LD = 68;
 constexpr int HEAD_HALF = 9;                        // patch slots per (row, column parity): no padding
 constexpr int HEAD_PLANE = 18 * 2 * HEAD_HALF;      // 324
 constexpr int HEAD_PATCH_SLOTS = 2 * HEAD_PLANE;    // 648 per k-step
 constexpr int HEAD_RING = 68;                       // ring pixels around a 16x16 block
-constexpr int HEAD_MAX_OUT = 4;                     // output channels per branch
+constexpr int HEAD_MAX_OUT = 4;                     // output channels per pass of a branch
 
 struct HeadArgs {
     const float *w2, *bias2;      // [total_out][3][3][64], [total_out]
@@ -963,6 +967,32 @@ __device__ __forceinline__ void head_own_ksplit(const float *hid, const float *w
     for (int r = 0; r < 4; ++r)
 #pragma unroll
         for (int c = 0; c < CB; ++c) part[r][c] = acc2[r][c].x + acc2[r][c].y;
+}
+
+// final weights of outputs [o, o + cb) -> LDS: cb x 9 x 64 floats, contiguous in w2
+__device__ __forceinline__ void head_load_w2(float *wts, const float *w2, int o, int cb, int tid) {
+    if (tid < cb * 144) reinterpret_cast<f32x4 *>(wts)[tid] = reinterpret_cast<const f32x4 *>(w2 + (size_t)o * 576)[tid];
+    if (tid + 256 < cb * 144)
+        reinterpret_cast<f32x4 *>(wts)[tid + 256] = reinterpret_cast<const f32x4 *>(w2 + (size_t)o * 576)[tid + 256];
+    if (tid + 512 < cb * 144)
+        reinterpret_cast<f32x4 *>(wts)[tid + 512] = reinterpret_cast<const f32x4 *>(w2 + (size_t)o * 576)[tid + 512];
+}
+
+// the ring owed to the neighbours by outputs [o, o + cb): one side per wave, only the three taps that can reach the block
+__device__ __forceinline__ void head_ring_store(const HeadArgs &ha, const float *hid, const float *wts, int tm, int o, int cb,
+                                                int wave, int lane) {
+    float accf[HEAD_MAX_OUT];
+    int ridx;
+    if (wave == 0) { ridx = lane; head_taps_n<2, 2, 0, 2>(cb, hid, wts, -1, lane - 1, accf); }
+    else if (wave == 1) { ridx = 18 + lane; head_taps_n<0, 0, 0, 2>(cb, hid, wts, 16, lane - 1, accf); }
+    else if (wave == 2) { ridx = 36 + lane; head_taps_n<0, 2, 2, 2>(cb, hid, wts, lane, -1, accf); }
+    else { ridx = 52 + lane; head_taps_n<0, 2, 0, 0>(cb, hid, wts, lane, 16, accf); }
+    if (lane < (wave < 2 ? 18 : 16)) {
+        float *rp = ha.ring + ((size_t)tm * ha.total_out + o) * HEAD_RING + ridx;
+#pragma unroll
+        for (int c = 0; c < HEAD_MAX_OUT; ++c)
+            if (c < cb) rp[c * HEAD_RING] = accf[c];
+    }
 }
 
 __global__ __launch_bounds__(256, 1) void conv_wino_head_kernel(const ConvArgs a, const HeadArgs ha) {
@@ -1075,13 +1105,9 @@ __global__ __launch_bounds__(256, 1) void conv_wino_head_kernel(const ConvArgs a
         const int lane_ = tid_ & 63, wave_ = __builtin_amdgcn_readfirstlane(tid_ >> 6);
         const int wm_ = wave_ >> 1, wn_ = wave_ & 1, h_ = lane_ >> 5, t_ = lane_ & 31;
         const int o0 = __builtin_amdgcn_readfirstlane(ha.out_begin[tn]);
-        const int cb = __builtin_amdgcn_readfirstlane(min(ha.out_begin[tn + 1] - o0, HEAD_MAX_OUT));
-        if (tid_ < cb * 144)            // cb x 9 x 64 floats, contiguous in w2
-            reinterpret_cast<f32x4 *>(wts)[tid_] = reinterpret_cast<const f32x4 *>(ha.w2 + (size_t)o0 * 576)[tid_];
-        if (tid_ + 256 < cb * 144)
-            reinterpret_cast<f32x4 *>(wts)[tid_ + 256] = reinterpret_cast<const f32x4 *>(ha.w2 + (size_t)o0 * 576)[tid_ + 256];
-        if (tid_ + 512 < cb * 144)
-            reinterpret_cast<f32x4 *>(wts)[tid_ + 512] = reinterpret_cast<const f32x4 *>(ha.w2 + (size_t)o0 * 576)[tid_ + 512];
+        const int cbt = __builtin_amdgcn_readfirstlane(ha.out_begin[tn + 1] - o0);       // outputs of the branch
+        const int cb = min(cbt, HEAD_MAX_OUT);
+        if (cbt <= HEAD_MAX_OUT) head_load_w2(wts, ha.w2, o0, cb, tid_);    // (a wider branch: after its further outputs)
         {
             const int col = tn * 64 + wn_ * 32 + t_;
             const float sc = a.scale ? a.scale[col] : 1.f, sh = a.bias ? a.bias[col] : 0.f;
@@ -1107,22 +1133,29 @@ __global__ __launch_bounds__(256, 1) void conv_wino_head_kernel(const ConvArgs a
                     }
             }
         }
+        if (cbt > HEAD_MAX_OUT) {
+            // outputs [HEAD_MAX_OUT, cbt) of a wide branch, while the hidden tile is whole: thread = pixel, all nine taps
+            for (int c0 = HEAD_MAX_OUT; c0 < cbt; c0 += HEAD_MAX_OUT) {
+                const int cbx = min(cbt - c0, HEAD_MAX_OUT);
+                head_load_w2(wts, ha.w2, o0 + c0, cbx, tid_);
+                __syncthreads();       // hidden tile and weights are in LDS
+                head_ring_store(ha, hid, wts, tm, o0 + c0, cbx, wave_, lane_);
+                const int py = tid_ >> 4, px = tid_ & 15;
+                float accx[HEAD_MAX_OUT];
+                head_taps_n<0, 2, 0, 2>(cbx, hid, wts, py, px, accx);
+                if (oy0_ + py < a.out_h && ox0_ + px < a.out_w) {
+                    float *op = ha.out + ((size_t)img * ha.total_out + o0 + c0) * plane + (size_t)(oy0_ + py) * a.out_w + ox0_ + px;
+#pragma unroll
+                    for (int c = 0; c < HEAD_MAX_OUT; ++c)
+                        if (c < cbx) op[c * plane] = accx[c] + ha.bias2[o0 + c0 + c];
+                }
+                __syncthreads();       // every wave is done with these weights
+            }
+            head_load_w2(wts, ha.w2, o0, cb, tid_);
+        }
         __syncthreads();               // (also waits for the weight loads above)
         // ---- final 3x3 conv of this branch from LDS -------------------------------------------------------
-        float accf[HEAD_MAX_OUT];
-        {   // the ring owed to the neighbours: one side per wave, only the three taps that can reach the block
-            int ridx;
-            if (wave_ == 0) { ridx = lane_; head_taps_n<2, 2, 0, 2>(cb, hid, wts, -1, lane_ - 1, accf); }
-            else if (wave_ == 1) { ridx = 18 + lane_; head_taps_n<0, 0, 0, 2>(cb, hid, wts, 16, lane_ - 1, accf); }
-            else if (wave_ == 2) { ridx = 36 + lane_; head_taps_n<0, 2, 2, 2>(cb, hid, wts, lane_, -1, accf); }
-            else { ridx = 52 + lane_; head_taps_n<0, 2, 0, 0>(cb, hid, wts, lane_, 16, accf); }
-            if (lane_ < (wave_ < 2 ? 18 : 16)) {
-                float *rp = ha.ring + ((size_t)tm * ha.total_out + o0) * HEAD_RING + ridx;
-#pragma unroll
-                for (int c = 0; c < HEAD_MAX_OUT; ++c)
-                    if (c < cb) rp[c * HEAD_RING] = accf[c];
-            }
-        }
+        head_ring_store(ha, hid, wts, tm, o0, cb, wave_, lane_);
         {   // own pixels, channel-split over the waves; partial sums meet in LDS (over the hidden tile)
             float part[4][HEAD_MAX_OUT];
             if (cb == 1) head_own_ksplit<1>(hid, wts, wave_, lane_, part);
