@@ -46,7 +46,9 @@ __global__ void __launch_bounds__(kT) labels_downsample_kernel(int B, int H, int
     const int b = (int)(t / oh);
     const unsigned char *p = gt + ((long long)b * H + (long long)y * f) * W + (long long)x * f;
     unsigned int m = 0;
-    if (f == 8 && (W & 7) == 0) {                       // the shipped configs: one 8-byte load per row of the block
+    // the shipped configs: one 8-byte load per row of the block (W % 8 == 0 keeps every row as aligned as the mask itself;
+    // a mask that does not start on an 8-byte boundary takes the byte loop)
+    if (f == 8 && (W & 7) == 0 && (reinterpret_cast<unsigned long long>(gt) & 7) == 0) {
         for (int r = 0; r < 8; ++r) {
             const uint2 v = *reinterpret_cast<const uint2 *>(p + (long long)r * W);
             unsigned int w0 = v.x, w1 = v.y;
@@ -126,7 +128,7 @@ __global__ void __launch_bounds__(kT) focal_kernel(FocalArgs a) {
         if (threadIdx.x == 0) s_div = tot;
         __syncthreads();
     }
-    const float gs = a.mean ? (float)((double)a.grad_scale / fmax(s_div, 0.0)) : a.grad_scale;   // 0 kept pixels: nan, as torch's mean of nothing
+    const float gs = a.mean ? (float)((double)a.grad_scale / fmax(s_div, 0.0)) : a.grad_scale;   // 0 kept pixels: inf, which no gradient is scaled by (the value is nan, as torch's mean of nothing)
     double acc = 0;
     const long long total = (long long)a.batch * a.pixels;
     for (long long e = blockIdx.x * (long long)kT + threadIdx.x; e < total; e += (long long)gridDim.x * kT) {
@@ -144,7 +146,8 @@ __global__ void __launch_bounds__(kT) focal_kernel(FocalArgs a) {
                 const float t = a.label_kind == 2 ? static_cast<const float *>(a.target)[off] : (lab == c ? 1.f : 0.f);
                 acc += (double)focal_elem(a.logit[off], t, a, g);
             }
-            if (a.grad) a.grad[off] = g * gs;
+            // an ignored pixel gets 0, not 0 * gs: with nothing kept gs is inf, and the reference scatters no gradient there
+            if (a.grad) a.grad[off] = keep ? g * gs : 0.f;
         }
     }
     const double s = block_sum_f64(acc, lds);
