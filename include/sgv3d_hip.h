@@ -1211,10 +1211,11 @@ int sgv3d_preprocess_mask(int frames, int in_h, int in_w, int channels, int rs_h
 
 #define SGV3D_FILTER_BICUBIC 0
 #define SGV3D_FILTER_LANCZOS 1
+#define SGV3D_FILTER_BILINEAR 2
 
-/* HOST function: sgv3d_resample_coeffs for Pillow's BICUBIC (a = -0.5, support 2) or LANCZOS (sinc(x) sinc(x / 3) on
- * [-3, 3)) filter, any downscale (ksize = 2 ceil(support max(in / out, 1)) + 1).  With bounds or coeffs NULL only *ksize
- * is written. */
+/* HOST function: sgv3d_resample_coeffs for Pillow's BICUBIC (a = -0.5, support 2), LANCZOS (sinc(x) sinc(x / 3) on
+ * [-3, 3)) or BILINEAR (the triangle 1 - |x|, support 1) filter, any downscale (ksize = 2 ceil(support max(in / out, 1)) + 1).
+ * With bounds or coeffs NULL only *ksize is written. */
 int sgv3d_resample_coeffs_filter(int filter, int in_size, int out_size, int32_t *bounds, int32_t *coeffs, int *ksize);
 
 /* One frame of an augmentation batch (112 bytes). */
@@ -1572,6 +1573,86 @@ int sgv3d_layernorm_bf16out(long long rows, int channels, const float *x, const 
 /* nn.GELU() on n bf16 values: sgv3d_gelu's f32 formulas (erf and erfc branches) on the widened value, rounded once (RNE): bitwise
  * sgv3d_gelu on the widened input followed by a cast.  y may be x. */
 int sgv3d_gelu_bf16(long long n, const void *x, void *y, void *stream);
+
+/* ================================================================================================
+ * SAM's prompt encoder and mask decoder (csrc/sam_decoder.hip): box prompts to class masks, inference only, f32.
+ * Linear layers, the two transposed convolutions, LayerNorm and GELU run through sgv3d_conv2d_forward, sgv3d_layernorm and
+ * sgv3d_gelu; these entries are the rest.  Every argument is checked on the host before any HIP call.  Vector stores only, no
+ * atomics: repeatable bit for bit, graph-capturable.
+ * ================================================================================================ */
+
+/* softmax(q k^T * scale) v per head, where ONE side is small: min(nq, nk) <= 16 (the decoder's 5 + 2 tokens).
+ *   q [batch, nq, q_ld], k [batch, nk, k_ld], v [batch, nk, v_ld], out [batch, nq, o_ld]: row strides in floats (multiples of
+ *   4, at least heads * head_dim); head h reads / writes columns [h * head_dim, (h + 1) * head_dim) of a row. */
+typedef struct sgv3d_sam_attn_desc {
+    int batch, nq, nk;
+    int heads, head_dim;        /* head_dim 16 or 32 */
+    int q_ld, k_ld, v_ld, o_ld;
+    float scale;                /* head_dim^-0.5 in the decoder; multiplies the finished dot product */
+} sgv3d_sam_attn_desc;
+
+/* HOST function: workspace bytes of sgv3d_sam_attention (0 for a rejected descriptor, for nk <= 16 and for nk <= 256). */
+size_t sgv3d_sam_attention_workspace_bytes(const sgv3d_sam_attn_desc *desc);
+
+/* nk <= 16: one query per lane, K and V of the (image, head) in LDS, one launch.  Otherwise nq <= 16: workgroup (split, head,
+ * image) takes 256 consecutive keys; with more than one split each writes (sum, max, weight sum) to the workspace and a second
+ * launch joins them by the online-softmax rule in split order.  Every output value is written; sums have a fixed order.
+ * Rejected by name (SGV3D_EINVAL): a null descriptor or pointer, a non-positive dimension, head_dim other than 16 / 32, both
+ * sides above 16, heads or batch above 65535, a row stride below heads * head_dim or not a multiple of 4, a non-finite scale,
+ * q / k / v / out / workspace not 16-byte aligned, a workspace that is too small. */
+int sgv3d_sam_attention(const sgv3d_sam_attn_desc *desc, const float *q, const float *k, const float *v, float *out, void *workspace,
+                        size_t workspace_bytes, void *stream);
+
+/* The decoder's token matrix of every box in one launch: tokens [boxes, 7, dim] = [iou_token, mask_tokens[0..3],
+ * pe(corner 0) + corner0, pe(corner 1) + corner1] with box f32 [boxes, 4] = (x0, y0, x1, y1) in the input frame (in_h x in_w,
+ * PromptEncoder.input_image_size): a corner is ((x + 0.5) / in_w, (y + 0.5) / in_h) and pe(c) = [sin(2 pi z), cos(2 pi z)],
+ * z = (2 c - 1) @ gauss, gauss f32 [2, dim / 2]; z, sin and cos are evaluated in f64 and rounded once. */
+int sgv3d_sam_prompt_tokens(int boxes, int dim, int in_h, int in_w, const float *box, const float *gauss, const float *corner0,
+                            const float *corner1, const float *iou_token, const float *mask_tokens, float *tokens, void *stream);
+
+/* PromptEncoder.get_dense_pe as an NHWC map: pe [h, w, dim], grid point (i, j) is pe(((j + 0.5) / w, (i + 0.5) / h)). */
+int sgv3d_sam_dense_pe(int h, int w, int dim, const float *gauss, float *pe, void *stream);
+
+/* out [boxes, pixels, channels] = emb[frame_of_box[b]] + vec: the decoder's src = image_embedding + dense prompt embedding, the
+ * embedding of a box's frame read by index (emb [frames, pixels, channels], frame_of_box device i32 [boxes], vec [channels]).
+ * The caller checks the indices; the kernel clamps them to [0, frames).  channels % 4 == 0. */
+int sgv3d_sam_gather_add(int boxes, int frames, long long pixels, int channels, const float *emb, const int32_t *frame_of_box,
+                         const float *vec, float *out, void *stream);
+
+/* out [boxes, n, pixels] = sum_c hyper[b, i, c] up[b, p, c]: the hypernetwork product (hyper [boxes] rows of hyper_ld floats
+ * holding [n, channels]; up [boxes, pixels, channels] NHWC).  n <= 4, channels % 4 == 0 and at most 1024. */
+int sgv3d_sam_hyper_product(int boxes, long long pixels, int channels, int n, int hyper_ld, const float *hyper, const float *up,
+                            float *out, void *stream);
+
+#define SGV3D_SAM_COMPOSE_CLASS 0 /* out u8 [frames, out_h, out_w]: get_sam_mask's class-id image                     */
+#define SGV3D_SAM_COMPOSE_BOOL 1  /* out u8 [boxes, out_h, out_w]: postprocess_masks(...) > 0                          */
+#define SGV3D_SAM_COMPOSE_LOGIT 2 /* out f32 [boxes, out_h, out_w]: postprocess_masks(...)                             */
+
+/* HOST function: workspace bytes of sgv3d_sam_mask_compose (the per-row and per-column tap tables). */
+size_t sgv3d_sam_mask_compose_workspace_bytes(int out_h, int out_w);
+
+/* Sam.postprocess_masks and the paint loop of get_sam_mask in one pass over the output pixels.  logits f32 [boxes, low, low]
+ * are bilinearly resized (align_corners=False) to [size, size], cropped to [pre_h, pre_w] and resized to [out_h, out_w]; the two
+ * resizes are composed: four (index, weight) pairs per axis, 16 taps per pixel, positions, weights and the sum in f64.  Neither
+ * the [boxes, size, size] nor the [boxes, out_h, out_w] float map is written.
+ *   CLASS: a pixel of frame f walks the boxes with frame_of_box[b] == f in order; the first with value > 0 and labels[b] != 0
+ *          owns it with min(max(labels[b], 0), 6); no such box: 0.  labels, frame_of_box: device i32 [boxes]; boxes may be 0.
+ *   BOOL / LOGIT: per box; labels and frame_of_box are not read. */
+int sgv3d_sam_mask_compose(int mode, int boxes, int frames, int low, int size, int pre_h, int pre_w, int out_h, int out_w,
+                           const float *logits, const int32_t *labels, const int32_t *frame_of_box, void *out, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
+/* HOST function: the same over host pointers through the same functions, pixel by pixel (CPU tests, sanitizer builds). */
+int sgv3d_sam_mask_compose_host(int mode, int boxes, int frames, int low, int size, int pre_h, int pre_w, int out_h, int out_w,
+                                const float *logits, const int32_t *labels, const int32_t *frame_of_box, void *out);
+
+/* Pillow's Image.resize with a coefficient table of sgv3d_resample_coeffs_filter (device copies), e.g. BILINEAR for
+ * ResizeLongestSide.apply_image: src u8 [frames, in_h, in_w, 3] -> horizontal integer pass into tmp u8 [frames, in_h, out_w, 3]
+ * -> vertical integer pass -> dst f32 [frames, 3, out_h, out_w] holding the u8 values (swap_rb: channel c goes to plane 2 - c).
+ * Table indices are clamped to the image. */
+int sgv3d_resize_u8_filter(int frames, int in_h, int in_w, int out_h, int out_w, const int32_t *xbounds, const int32_t *xcoeffs,
+                           int xksize, const int32_t *ybounds, const int32_t *ycoeffs, int yksize, int swap_rb, const uint8_t *src,
+                           uint8_t *tmp, float *dst, void *stream);
 
 #ifdef __cplusplus
 }

@@ -26,6 +26,11 @@ class VitAttnDesc(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("batch", "height", "width", "heads", "head_dim", "win_h", "win_w")]
 
 
+class SamAttnDesc(ctypes.Structure):
+    """Mirror of ``sgv3d_sam_attn_desc`` (include/sgv3d_hip.h)."""
+    _fields_ = [(n, c_int) for n in ("batch", "nq", "nk", "heads", "head_dim", "q_ld", "k_ld", "v_ld", "o_ld")] + [("scale", ctypes.c_float)]
+
+
 CONV_NORMAL, CONV_DECONV, CONV_NCHW_OUT, CONV_GROUP_PLANES = 0, 1, 2, 3
 TILE_AUTO, TILE_128x128, TILE_128x64, TILE_64x128, TILE_64x64 = 0, 1, 2, 3, 4
 
@@ -263,6 +268,16 @@ _PROTOS = {
     "sgv3d_vit_attention_bf16": (c_int, [ctypes.POINTER(VitAttnDesc)] + [c_void_p] * 6),
     "sgv3d_layernorm_bf16out": (c_int, [c_ll, c_int] + [c_void_p] * 3 + [ctypes.c_float, c_void_p, c_void_p]),
     "sgv3d_gelu_bf16": (c_int, [c_ll, c_void_p, c_void_p, c_void_p]),
+    "sgv3d_sam_attention_workspace_bytes": (c_size_t, [ctypes.POINTER(SamAttnDesc)]),
+    "sgv3d_sam_attention": (c_int, [ctypes.POINTER(SamAttnDesc)] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "sgv3d_sam_prompt_tokens": (c_int, [c_int] * 4 + [c_void_p] * 8),
+    "sgv3d_sam_dense_pe": (c_int, [c_int] * 3 + [c_void_p] * 3),
+    "sgv3d_sam_gather_add": (c_int, [c_int, c_int, c_ll, c_int] + [c_void_p] * 5),
+    "sgv3d_sam_hyper_product": (c_int, [c_int, c_ll, c_int, c_int, c_int] + [c_void_p] * 4),
+    "sgv3d_sam_mask_compose_workspace_bytes": (c_size_t, [c_int] * 2),
+    "sgv3d_sam_mask_compose": (c_int, [c_int] * 9 + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "sgv3d_sam_mask_compose_host": (c_int, [c_int] * 9 + [c_void_p] * 4),
+    "sgv3d_resize_u8_filter": (c_int, [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 4),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -52,7 +52,13 @@ double lanczos_filter(double x) {     // Resample.c lanczos_filter: truncated si
     return 0.0;
 }
 
-double filter_support(int filter) { return filter == SGV3D_FILTER_LANCZOS ? 3.0 : 2.0; }
+double bilinear_filter(double x) {    // Resample.c bilinear_filter: the triangle, support 1
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return 1.0 - x;
+    return 0.0;
+}
+
+double filter_support(int filter) { return filter == SGV3D_FILTER_LANCZOS ? 3.0 : filter == SGV3D_FILTER_BILINEAR ? 1.0 : 2.0; }
 
 int ksize_of(int filter, int in_size, int out_size) {
     const double scale = (double)in_size / out_size;
@@ -430,7 +436,7 @@ int launch(const char *what, int frames, int in_h, int in_w, int chans, const sg
 
 extern "C" int sgv3d_resample_coeffs_filter(int filter, int in_size, int out_size, int32_t *bounds, int32_t *coeffs,
                                             int *ksize) {
-    SGV3D_REQUIRE(filter == SGV3D_FILTER_BICUBIC || filter == SGV3D_FILTER_LANCZOS,
+    SGV3D_REQUIRE(filter == SGV3D_FILTER_BICUBIC || filter == SGV3D_FILTER_LANCZOS || filter == SGV3D_FILTER_BILINEAR,
                   "resample_coeffs_filter: unknown filter %d", filter);
     SGV3D_REQUIRE(in_size > 0 && out_size > 0, "resample_coeffs_filter: non-positive size (%d -> %d)", in_size,
                   out_size);
@@ -438,7 +444,7 @@ extern "C" int sgv3d_resample_coeffs_filter(int filter, int in_size, int out_siz
     if (ksize) *ksize = ks;
     if (!bounds || !coeffs) return SGV3D_OK;
     // Pillow's precompute_coeffs + normalize_coeffs_8bpc (Resample.c), box = the whole input
-    double (*fn)(double) = filter == SGV3D_FILTER_LANCZOS ? lanczos_filter : bicubic_filter;
+    double (*fn)(double) = filter == SGV3D_FILTER_LANCZOS ? lanczos_filter : filter == SGV3D_FILTER_BILINEAR ? bilinear_filter : bicubic_filter;
     const double scale = (double)in_size / out_size;
     const double fs = scale < 1.0 ? 1.0 : scale;
     const double support = filter_support(filter) * fs, ss = 1.0 / fs;

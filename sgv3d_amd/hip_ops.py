@@ -359,6 +359,17 @@ def vit_bf16_active(dim, num_heads, mlp_dim=None):
     return bool(VIT_BF16 and MFMA_BF16 and not MFMA_F32X3 and vit_bf16_covers(dim, num_heads, mlp_dim))
 
 
+def sam_decoder_covers(transformer_dim, num_heads, downsample_rate=2):
+    """Whether the SAM mask decoder's kernels take a two-way transformer of this shape: sgv3d_sam_attention has head dimensions 16
+    and 32, so transformer_dim / num_heads (self-attention) and transformer_dim / downsample_rate / num_heads (the cross
+    attentions) must each be one of them; transformer_dim % 32 == 0 keeps the upscaled map's transformer_dim / 8 channels in
+    16-byte rows.  SAM's 256 / 8 / 2 is covered.  An uncovered decoder raises before any launch."""
+    d, h, r = int(transformer_dim), int(num_heads), int(downsample_rate)
+    if d <= 0 or h <= 0 or r <= 0 or d % 32 or d % r or d % h or (d // r) % h:
+        return False
+    return d // h in (16, 32) and d // r // h in (16, 32)
+
+
 def activation_dtype(*channel_counts):
     """torch.bfloat16 when bf16 mode keeps activations as bf16 tensors in HBM (MFMA_BF16 and BF16_ACTIVATIONS, not the f32x3
     split) and every given channel count allows 16-byte bf16 rows (multiple of 8); else None (= float32 tensors)."""

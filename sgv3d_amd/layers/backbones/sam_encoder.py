@@ -205,6 +205,22 @@ class ImageEncoderViT(nn.Module):
             x = self.neck[3].forward_nhwc(x)
             return self.batch_postprocess(x)
 
+    def embed(self, x: torch.Tensor) -> torch.Tensor:
+        """SAM's own forward, without the reference's crop and resize: [B, 3, H, W] with long side ``img_size`` -> the NHWC neck
+        output [B, img_size / 16, img_size / 16, out_chans] that the mask decoder of sgv3d_amd.segment_anything reads."""
+        require_device(x, "ImageEncoderViT")
+        if self.pixel_mean.device != x.device or self.patch_embed.proj.weight.device != x.device:
+            raise _lib.SGV3DError(f"ImageEncoderViT: parameters on {self.patch_embed.proj.weight.device}, input on {x.device}")
+        with torch.no_grad():
+            x = self.batch_preprocess(x)
+            x = self.patch_embed(x, residual=None if self.pos_embed is None else self._pos_residual(int(x.shape[0])))
+            for blk in self.blocks:
+                x = blk(x)
+            x = self._neck1.get(self.neck[0].weight)(x)
+            x = self.neck[1].forward_nhwc(x)
+            x = self._neck2.get(self.neck[2].weight, pad=1)(x)
+            return self.neck[3].forward_nhwc(x)
+
 
 class Block(nn.Module):
     """Transformer block with window attention (``window_size`` > 0) or global attention (0)."""

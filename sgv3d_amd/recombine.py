@@ -7,8 +7,10 @@ camera.  ``FrameRecombiner`` does the same on frames that are already on the GPU
 four launches per batch; its frames and masks go straight into ``TrainAugmenter`` / ``ImagePreprocessor.mask`` (online
 copy-paste augmentation) or through ``write`` into the generated split (offline).
 
-SAM is not run: each frame's stored class-id mask (``mask_image // 40``, values 0..6, what the reference's first stage
-writes) stands in for the masks SAM would draw inside the accepted boxes.
+The class-id masks (values 0..6) come from the caller.  ``sgv3d_amd.sam_masks.get_sam_mask`` / ``mask_images`` draw them with SAM
+on the device as the reference does; the stand-in of DESIGN.md section 17 remains available: each frame's
+stored mask (``mask_image // 40``, what the reference's first stage writes) in place of the masks SAM would draw inside the
+accepted boxes.  SAM's weights are still not available to this project, so nothing here has run with them.
 
 There is no CPU path: ``combine`` needs the GPU.  ``load_sample``, ``sample_order`` and ``write`` are host file handling.
 """
