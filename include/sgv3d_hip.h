@@ -1082,6 +1082,34 @@ int sgv3d_focal_loss_with_logits(int batch, int num_classes, int pixels, const f
                                  int reduction_mean, float grad_scale, float *grad, float *loss_out, void *workspace,
                                  size_t workspace_bytes, void *stream);
 
+/* DiceLoss.forward (losses/dice.py:57-130) over soft_dice_score (losses/_functional.py:172-187): value and input gradient
+ * (csrc/dice_loss.hip).
+ *   pred f32, element (b, c, p) at b*batch_stride + c*class_stride + p*pixel_stride (floats), as for
+ *   sgv3d_focal_loss_with_logits; target_kind 0: u8 class ids [B, P], 1: int64 class ids [B, P] (t = (id == c); an id equal
+ *   to ignore_index masks the pixel when use_ignore_index; any other id outside [0, C) matches no class), 2: f32 targets
+ *   addressed like pred (an element equal to ignore_index is masked); activation 0: pred holds probabilities, 1: sigmoid,
+ *   2: softmax over the classes (2 <= C <= 32, class ids only; class ids need it).
+ *   Per class over the kept elements: I = sum p*t, P = sum p, T = sum t, score = (2 I + smooth) / max(P + T + smooth, eps),
+ *   loss_c = log_loss ? -log(max(score, eps)) : 1 - score, zero where T == 0; loss_out[0] = sum_c class_weight[c] * loss_c
+ *   (class_weight f32 [C], device: the multiplicity of c in the reference's `classes` list / its length, or 1/C).
+ *   saved f64 [C][4] (device): I, P, T and d loss / d score_c -- what sgv3d_dice_loss_backward needs.
+ *   forward: two launches (partial sums over a fixed grid; a one-workgroup finish), float64 sums in a fixed order.
+ *   backward: one launch; grad (addressed like pred) receives upstream[0] * d loss / d pred in every element of the view;
+ *   upstream f32 [1] on the device, NULL = 1.  No host wait anywhere: both calls can be captured in a hipGraph.
+ *   workspace: sgv3d_dice_loss_workspace_bytes(num_classes) bytes (host-side; 0 for num_classes <= 0).
+ *   Refused before any launch: sizes <= 0, a null pointer, target_kind or activation out of range, activation 2 with C
+ *   outside 2..32 or with f32 targets, class ids with another activation (SGV3D_EINVAL); a short workspace (SGV3D_ENOSPACE). */
+size_t sgv3d_dice_loss_workspace_bytes(int num_classes);
+int sgv3d_dice_loss_forward(int batch, int num_classes, int pixels, const float *pred, long long batch_stride,
+                            long long class_stride, long long pixel_stride, const void *target, int target_kind,
+                            int activation, long long ignore_index, int use_ignore_index, double smooth, double eps,
+                            int log_loss, const float *class_weight, float *loss_out, double *saved, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int sgv3d_dice_loss_backward(int batch, int num_classes, int pixels, const float *pred, long long batch_stride,
+                             long long class_stride, long long pixel_stride, const void *target, int target_kind,
+                             int activation, long long ignore_index, int use_ignore_index, double smooth, double eps,
+                             const double *saved, const float *upstream, float *grad, void *stream);
+
 /* Adjoint of sgv3d_upsample_bilinear2x: dy f32 [B, 2H, 2W, C] -> dx f32 [B, H, W, C] (any C). */
 int sgv3d_upsample_bilinear2x_backward(int batch, int h, int w, int channels, const float *dy, float *dx, void *stream);
 

@@ -359,6 +359,16 @@ def vit_bf16_active(dim, num_heads, mlp_dim=None):
     return bool(VIT_BF16 and MFMA_BF16 and not MFMA_F32X3 and vit_bf16_covers(dim, num_heads, mlp_dim))
 
 
+def dice_covers(mode, num_classes):
+    """Whether losses.DiceLoss takes this mode and class count: 'multiclass' keeps one pixel's classes in a thread's registers
+    (csrc/dice_loss.hip), which covers 2..32 classes (SGV3D has 7); 'binary' and 'multilabel' walk the classes and take any
+    count.  An uncovered combination raises before any launch."""
+    c = int(num_classes)
+    if mode == "multiclass":
+        return 2 <= c <= 32
+    return mode in ("binary", "multilabel") and c >= 1
+
+
 def sam_decoder_covers(transformer_dim, num_heads, downsample_rate=2):
     """Whether the SAM mask decoder's kernels take a two-way transformer of this shape: sgv3d_sam_attention has head dimensions 16
     and 32, so transformer_dim / num_heads (self-attention) and transformer_dim / downsample_rate / num_heads (the cross

@@ -7,6 +7,10 @@ id of each 8x8 block; the stride-16 logits are bilinearly upsampled x2; both map
 (alpha 0.25, gamma 2, mean) and the two values are averaged.  Three kernels instead of the reference's ~40 torch
 kernels per map: ``sgv3d_semantic_labels_downsample``, ``sgv3d_upsample_bilinear2x`` (+ its adjoint) and
 ``sgv3d_focal_loss_with_logits``.
+
+``dice_weight > 0`` adds the dice term the experiment files carry next to the focal one: each map's loss becomes
+``focal + dice_weight * DiceLoss('multiclass', **dice_kwargs)`` on the same logits and the same uint8 labels (two more
+launches per map forward, one backward: csrc/dice_loss.hip).  With the default 0 no DiceLoss exists and nothing changes.
 """
 import torch
 from torch import nn
@@ -14,6 +18,7 @@ from torch import nn
 from .. import _lib
 from ..bsm_grad import upsample_bilinear2x
 from ..hip_ops import prof
+from .dice import DiceLoss
 from .focal import FocalLoss
 
 __all__ = ['SemanticSupervision', 'downsample_gt_semantic']
@@ -37,15 +42,23 @@ class SemanticSupervision(nn.Module):
     """``get_loss(img_preds, gt_semantic)`` of the BSM experiment (:291-302).  ``img_preds`` = (semantic0, semantic1):
     the logits ``[B*N, classes, h, w]`` the training forward returns (NCHW views of channel-last buffers)."""
 
-    def __init__(self, downsample=8, alpha=0.25, gamma=2.0):
+    def __init__(self, downsample=8, alpha=0.25, gamma=2.0, dice_weight=0.0, dice_kwargs=None):
         super().__init__()
         self.downsample = downsample
         self.focal_loss = FocalLoss(mode='multiclass', alpha=alpha, gamma=gamma, reduction="mean")    # :249
+        self.dice_weight = float(dice_weight)
+        self.dice_loss = DiceLoss('multiclass', **(dice_kwargs or {})) if self.dice_weight != 0 else None
+
+    def _map_loss(self, logits, labels):
+        loss = self.focal_loss(logits, labels)
+        if self.dice_loss is not None:
+            loss = loss + self.dice_weight * self.dice_loss(logits, labels)
+        return loss
 
     def forward(self, img_preds, gt_semantic):
         semantic0, semantic1 = img_preds
         up = upsample_bilinear2x(semantic0.permute(0, 2, 3, 1))             # NHWC in, NHWC out (:293)
         labels = downsample_gt_semantic(gt_semantic, self.downsample)       # :295
-        loss0 = self.focal_loss(up.permute(0, 3, 1, 2), labels)             # :297
-        loss1 = self.focal_loss(semantic1, labels)                          # :298
+        loss0 = self._map_loss(up.permute(0, 3, 1, 2), labels)              # :297
+        loss1 = self._map_loss(semantic1, labels)                           # :298
         return (loss0 + loss1) / 2                                          # :299

@@ -41,6 +41,8 @@ ap.add_argument("--no-fuse-dcn", action="store_true", help="the deformable convo
                 "tensor kept for backward) instead of misc_grad.deform_conv3x3 (hip_ops.DCN_FUSED_TRAIN)")
 ap.add_argument("--checkpoint", default=None, help="after the timed steps: time save_checkpoint to this file and load_checkpoint "
                 "back into the model and optimiser (sgv3d_amd/checkpoint.py)")
+ap.add_argument("--dice-weight", type=float, default=0.0, help="BSM configs: add dice_weight x DiceLoss('multiclass') to each semantic map's "
+                "focal loss (losses.SemanticSupervision); 0 = the focal loss alone")
 args = ap.parse_args()
 
 hip_ops.DCN_FUSED_TRAIN = not args.no_fuse_dcn
@@ -73,7 +75,7 @@ boxes, labels = synthetic.make_gt(args.batch, seed=group.rank, n_range=(10, 40),
 boxes, labels = [b.to(dev) for b in boxes], [l.to(dev) for l in labels]
 if BSM:
     from sgv3d_amd.losses import SemanticSupervision
-    semantic = SemanticSupervision(8)
+    semantic = SemanticSupervision(8, dice_weight=args.dice_weight)
     gt_semantic = torch.randint(0, 7, (args.batch, 1) + tuple(bconf['final_dim']), dtype=torch.uint8,
                                 generator=torch.Generator().manual_seed(group.rank)).to(dev)
 opt = DataParallelAdamW(model.parameters(), lr=reference_lr(args.batch, group.world), max_grad_norm=args.clip or None,
@@ -160,7 +162,7 @@ out = {"metric": "training samples/s (forward + loss + backward + all-reduce + A
        "batch_per_gpu": args.batch, "global_batch": args.batch * group.world, "dtype": args.dtype,
        "world_size": group.dist.get_world_size() if group.dist is not None else 1, "backend": group.backend,
        "allreduce_bytes_per_step": 4 * sum(g.numel() for _, g, _ in opt.flat.buckets), "allreduce_buckets": len(opt.flat.buckets),
-       "allreduce_overlapped_with_backward": not args.no_overlap, "parameters": nparam, "loss": float(loss.detach()), "config": args.config, "loss_trace": TRACE or None, "graph": bool(args.graph), "graph_replays": graphed.replays if args.graph else 0,
+       "allreduce_overlapped_with_backward": not args.no_overlap, "parameters": nparam, "loss": float(loss.detach()), "config": args.config, "dice_weight": args.dice_weight if BSM else None, "loss_trace": TRACE or None, "graph": bool(args.graph), "graph_replays": graphed.replays if args.graph else 0,
        "update_in_graph": bool(graphed.in_graph_update) if args.graph else None, "optimizer_steps": opt.steps,
        "peak_mem_gb": torch.cuda.max_memory_allocated(dev) / 2**30, "data": "synthetic",
        "fuse_lift_splat": bool(model.backbone.fuse_lift_splat),
