@@ -1521,7 +1521,7 @@ int sgv3d_kitti_eval_device_host(int num_images, int total_gt, int total_dt, lon
                                  double *thresholds);
 
 /* ================================================================================================
- * SAM's ViT image encoder (csrc/vit.hip): layers/backbones/sam_encoder.py of the reference, inference only.
+ * SAM's ViT image encoder (csrc/vit.hip): layers/backbones/sam_encoder.py of the reference; the adjoints follow below.
  * Every linear layer and convolution of the encoder runs through sgv3d_conv2d_forward; these five entries are the rest.
  * Vector stores only, no float atomics: repeatable bit for bit.  f32 tensors; every tensor pointer 16-byte aligned.
  * ================================================================================================ */
@@ -1570,6 +1570,66 @@ int sgv3d_vit_preprocess(int batch, int height, int width, const float *img, con
  * the four-tap sum are evaluated in f64 and rounded once. */
 int sgv3d_resize_bilinear(int batch, int h, int w, int channels, int crop_h, int crop_w, int out_h, int out_w, const float *x,
                           float *y, void *stream);
+
+/* ================================================================================================
+ * Training the ViT encoder (csrc/vit_grad.hip): the adjoints of the entries above, f32 tensors, every pointer 16-byte aligned.
+ * Every argument is checked on the host before any HIP call (SGV3D_EINVAL by name; a short workspace is SGV3D_ENOSPACE).  No
+ * float atomics, vector stores only, a fixed summation order: every entry is repeatable bit for bit, and graph-capturable (no
+ * host wait, no allocation).  Linear layers and convolutions take their gradients from the conv entries.
+ * ================================================================================================ */
+
+/* sgv3d_vit_attention that also writes lse [batch, heads, height, width]: the row maximum plus the log of the row sum of the
+ * logits as the kernel forms them.  The same kernel body: `out` is bit for bit what sgv3d_vit_attention writes.  Rejects what
+ * sgv3d_vit_attention rejects, and a null or misaligned lse. */
+int sgv3d_vit_attention_lse(const sgv3d_vit_attn_desc *desc, const float *qkv, const float *pad_qkv, const float *rel_pos_h,
+                            const float *rel_pos_w, float *out, float *lse, void *stream);
+
+/* The adjoint of sgv3d_vit_attention: the same descriptor, window / padding-token / relative-position semantics and head
+ * dimensions.  With i over the real tokens of a window, j over all win_h * win_w slots (a padding slot carries pad_qkv, or
+ * zeros), scale = head_dim^-0.5:
+ *   S_ij = scale q_i.k_j + q_i.Rh[ih - jh + win_h - 1] + q_i.Rw[iw - jw + win_w - 1]     P_ij = exp(S_ij - lse_i)
+ *   dS_ij = P_ij (dO_i.v_j - dO_i.O_i)      dv_j = sum_i P_ij dO_i      dk_j = scale sum_i dS_ij q_i
+ *   A_h[i,a] = sum_{j: jh = a} dS_ij        A_w[i,b] = sum_{j: jw = b} dS_ij
+ *   dq_i = scale sum_j dS_ij k_j + sum_a A_h[i,a] Rh[ih - a + win_h - 1] + sum_b A_w[i,b] Rw[iw - b + win_w - 1]
+ *   dRh[r] = sum over images, heads, windows and {i, a: ih - a + win_h - 1 = r} of A_h[i,a] q_i      (dRw likewise)
+ * A padding slot is never a query.
+ *   out, lse     what sgv3d_vit_attention_lse wrote for the same arguments         dout [batch, height, width, heads * head_dim]
+ *   dqkv         [batch, height, width, 3 * heads * head_dim]: every element written exactly once
+ *   dpad_qkv     [3 * heads * head_dim]: the q part exactly 0; the k and v parts the sums of dk_j, dv_j over every padding slot
+ *                of every window, image and head.  NULL is allowed when pad_qkv is NULL.
+ *   drel_pos_h   [2 * win_h - 1, head_dim], drel_pos_w [2 * win_w - 1, head_dim]: given exactly when the tables are
+ * No tensor of size tokens x keys exists: P is recomputed tile by tile from lse.  S, dP, dv, dk and the k part of dq are
+ * v_mfma_f32_16x16x4_f32 products; the relative-position products (per query win_h + win_w table rows) are plain f32 FMAs.
+ * Launches: a preparation pass (dO.O, q.Rh, q.Rw into the workspace), one launch that owns key tiles (dk, dv, the padding sums),
+ * one that owns query tiles (dq, A_h, A_w), the table partials, and a finish that adds the per-workgroup partials in workgroup
+ * order.  The workspace holds O(slots * (win_h + win_w)) floats per (image, head, window); its content on entry is ignored.
+ * sgv3d_vit_attention_backward_workspace_bytes is 0 for a descriptor the call would reject, and covers the call with tables.
+ * A call whose slots (images * heads * windows * slots rounded up to 64) reach 2^31 is rejected. */
+size_t sgv3d_vit_attention_backward_workspace_bytes(const sgv3d_vit_attn_desc *desc);
+int sgv3d_vit_attention_backward(const sgv3d_vit_attn_desc *desc, const float *qkv, const float *pad_qkv, const float *rel_pos_h,
+                                 const float *rel_pos_w, const float *out, const float *lse, const float *dout, float *dqkv,
+                                 float *dpad_qkv, float *drel_pos_h, float *drel_pos_w, void *workspace, size_t workspace_bytes,
+                                 void *stream);
+
+/* The adjoint of sgv3d_layernorm (nn.LayerNorm and LayerNorm2d on NHWC): mean and rstd are recomputed from x with the forward's
+ * two-pass f64 sums; dx = rstd (g - mean(g) - xhat mean(g xhat)) with g = dy * weight and the row sums in f64; dweight = sum
+ * over rows of dy * xhat and dbias = sum over rows of dy go through f64 partials of 32 rows each and a finish in chunk order.
+ * channels % 4 == 0, any row count.  dx must not overlap x or dy (the weight and bias partials read both after dx is written):
+ * an overlap is rejected. */
+size_t sgv3d_layernorm_backward_workspace_bytes(long long rows, int channels);
+int sgv3d_layernorm_backward(long long rows, int channels, const float *x, const float *weight, float eps, const float *dy, float *dx,
+                             float *dweight, float *dbias, void *workspace, size_t workspace_bytes, void *stream);
+
+/* The adjoint of sgv3d_gelu: dx = dy (Phi(x) + x phi(x)), the exact erf form (erfc in the left tail, as the forward), x the
+ * pre-activation.  dx may be dy. */
+int sgv3d_gelu_backward(long long n, const float *x, const float *dy, float *dx, void *stream);
+
+/* The adjoint of sgv3d_resize_bilinear in gather form: dx [batch, h, w, channels] from dy [batch, out_h, out_w, channels]; each
+ * input pixel sums the output pixels that read it, dx[i,j] = sum_o sum_p wy[o,i] wx[p,j] dy[o,p], with the per-axis taps
+ * evaluated in f64 exactly as the forward evaluates them and the sum in f64, rounded once.  Rows and columns outside the crop
+ * are zero; every element of dx is written once. */
+int sgv3d_resize_bilinear_backward(int batch, int h, int w, int channels, int crop_h, int crop_w, int out_h, int out_w, const float *dy,
+                                   float *dx, void *stream);
 
 /* ================================================================================================
  * The encoder's bf16 mode (csrc/vit_bf16.hip, hip_ops.VIT_BF16): between the two residual adds of a block every tensor is

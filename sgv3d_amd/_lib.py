@@ -271,6 +271,13 @@ _PROTOS = {
     "sgv3d_gelu": (c_int, [c_ll, c_void_p, c_void_p, c_void_p]),
     "sgv3d_vit_preprocess": (c_int, [c_int] * 3 + [c_void_p] * 3 + [c_int, c_void_p, c_void_p]),
     "sgv3d_resize_bilinear": (c_int, [c_int] * 8 + [c_void_p] * 3),
+    "sgv3d_vit_attention_lse": (c_int, [ctypes.POINTER(VitAttnDesc)] + [c_void_p] * 7),
+    "sgv3d_vit_attention_backward_workspace_bytes": (c_size_t, [ctypes.POINTER(VitAttnDesc)]),
+    "sgv3d_vit_attention_backward": (c_int, [ctypes.POINTER(VitAttnDesc)] + [c_void_p] * 12 + [c_size_t, c_void_p]),
+    "sgv3d_layernorm_backward_workspace_bytes": (c_size_t, [c_ll, c_int]),
+    "sgv3d_layernorm_backward": (c_int, [c_ll, c_int, c_void_p, c_void_p, ctypes.c_float] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "sgv3d_gelu_backward": (c_int, [c_ll] + [c_void_p] * 4),
+    "sgv3d_resize_bilinear_backward": (c_int, [c_int] * 8 + [c_void_p] * 3),
     "sgv3d_vit_attention_bf16": (c_int, [ctypes.POINTER(VitAttnDesc)] + [c_void_p] * 6),
     "sgv3d_layernorm_bf16out": (c_int, [c_ll, c_int] + [c_void_p] * 3 + [ctypes.c_float, c_void_p, c_void_p]),
     "sgv3d_gelu_bf16": (c_int, [c_ll, c_void_p, c_void_p, c_void_p]),

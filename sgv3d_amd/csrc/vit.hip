@@ -8,6 +8,11 @@
 
 using namespace sgv3d;
 
+namespace sgv3d {
+int vit_attention_impl(const sgv3d_vit_attn_desc *desc, const float *qkv, const float *pad_qkv, const float *rel_pos_h,
+                       const float *rel_pos_w, float *out, float *lse, void *stream);
+}
+
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -45,6 +50,7 @@ struct AttnParams {
     float scale, inv_win_w;
     const float *qkv, *pad, *rh, *rw;
     float *out;
+    float *lse;      // LSE kernels only: [B, nH, H, W], row maximum + log of the row sum
 };
 
 template <int HD>
@@ -54,7 +60,7 @@ struct AttnGeom {
     static constexpr int floats = kKT * (LDK + LDV);
 };
 
-template <int HD>
+template <int HD, bool LSE>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HD <= 64 ? 3 : 2))) void vit_attention_kernel(AttnParams p) {
     constexpr int LDK = AttnGeom<HD>::LDK, LDV = AttnGeom<HD>::LDV;
     constexpr int NC = HD / 16;  // 16-byte operand reads per key row of QK^T (four k-steps each)
@@ -266,6 +272,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HD <= 64
     l += __shfl_xor(l, 32);
     const int oh = h0 + qh, ow = w0 + qw;
     if (q_live && oh < p.H && ow < p.W) {
+        if (LSE && g == 0) p.lse[(((size_t)b * p.nH + head) * p.H + oh) * p.W + ow] = m + logf(l);
         // row 4 g + r of accumulator 4 c + i is d = 64 c + 4 (4 g + r) + i: sixteen consecutive floats per lane and c
         float *dst = p.out + ((size_t)((size_t)b * p.H + oh) * p.W + ow) * (size_t)C + head * HD;
 #pragma unroll
@@ -289,13 +296,19 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HD <= 64
     }
 }
 
+template <int HD, bool LSE>
+int launch_attention_lse(const AttnParams &p, int blocks, size_t lds_bytes, hipStream_t stream) {
+    static PerDeviceSize state;
+    if (!ensure_dynamic_lds(reinterpret_cast<const void *>(vit_attention_kernel<HD, LSE>), lds_bytes, state))
+        return fail(SGV3D_ELAUNCH, "vit_attention: cannot reserve %zu bytes of LDS", lds_bytes);
+    hipLaunchKernelGGL((vit_attention_kernel<HD, LSE>), dim3(blocks), dim3(kBlock), lds_bytes, stream, p);
+    return check_launch("vit_attention_kernel");
+}
+
+// LSE is a template parameter: the instantiation without it is the kernel as it was, instruction for instruction
 template <int HD>
 int launch_attention(const AttnParams &p, int blocks, size_t lds_bytes, hipStream_t stream) {
-    static PerDeviceSize state;
-    if (!ensure_dynamic_lds(reinterpret_cast<const void *>(vit_attention_kernel<HD>), lds_bytes, state))
-        return fail(SGV3D_ELAUNCH, "vit_attention: cannot reserve %zu bytes of LDS", lds_bytes);
-    hipLaunchKernelGGL(vit_attention_kernel<HD>, dim3(blocks), dim3(kBlock), lds_bytes, stream, p);
-    return check_launch("vit_attention_kernel");
+    return p.lse ? launch_attention_lse<HD, true>(p, blocks, lds_bytes, stream) : launch_attention_lse<HD, false>(p, blocks, lds_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -412,8 +425,9 @@ __global__ __launch_bounds__(kBlock) void resize_bilinear_kernel(int B, int h, i
 
 }  // namespace
 
-extern "C" int sgv3d_vit_attention(const sgv3d_vit_attn_desc *desc, const float *qkv, const float *pad_qkv,
-                                   const float *rel_pos_h, const float *rel_pos_w, float *out, void *stream) {
+// sgv3d_vit_attention, and with `lse` sgv3d_vit_attention_lse (csrc/vit_grad.hip): one body, so `out` has the same bits in both
+int sgv3d::vit_attention_impl(const sgv3d_vit_attn_desc *desc, const float *qkv, const float *pad_qkv, const float *rel_pos_h,
+                              const float *rel_pos_w, float *out, float *lse, void *stream) {
     SGV3D_REQUIRE(desc, "vit_attention: null descriptor");
     const sgv3d_vit_attn_desc &d = *desc;
     SGV3D_REQUIRE(d.batch > 0 && d.height > 0 && d.width > 0 && d.heads > 0 && d.head_dim > 0 && d.win_h > 0 && d.win_w > 0,
@@ -439,7 +453,7 @@ extern "C" int sgv3d_vit_attention(const sgv3d_vit_attn_desc *desc, const float 
     p.tw_ld = rel ? (d.win_w | 1) : 0;
     p.scale = 1.0f / sqrtf((float)d.head_dim);
     p.inv_win_w = 1.0f / (float)d.win_w;
-    p.qkv = qkv, p.pad = pad_qkv, p.rh = rel_pos_h, p.rw = rel_pos_w, p.out = out;
+    p.qkv = qkv, p.pad = pad_qkv, p.rh = rel_pos_h, p.rw = rel_pos_w, p.out = out, p.lse = lse;
     const long long blocks = (long long)d.batch * d.heads * p.nwy * p.nwx * p.nqt;
     SGV3D_REQUIRE(blocks < (1LL << 31), "vit_attention: too many workgroups");
     const int kv_floats = d.head_dim == 32 ? AttnGeom<32>::floats : d.head_dim == 64 ? AttnGeom<64>::floats : AttnGeom<80>::floats;
@@ -450,6 +464,11 @@ extern "C" int sgv3d_vit_attention(const sgv3d_vit_attn_desc *desc, const float 
         case 64: return launch_attention<64>(p, (int)blocks, lds_bytes, s);
         default: return launch_attention<80>(p, (int)blocks, lds_bytes, s);
     }
+}
+
+extern "C" int sgv3d_vit_attention(const sgv3d_vit_attn_desc *desc, const float *qkv, const float *pad_qkv,
+                                   const float *rel_pos_h, const float *rel_pos_w, float *out, void *stream) {
+    return vit_attention_impl(desc, qkv, pad_qkv, rel_pos_h, rel_pos_w, out, nullptr, stream);
 }
 
 extern "C" int sgv3d_layernorm(long long rows, int channels, const float *x, const float *weight, const float *bias, float eps,

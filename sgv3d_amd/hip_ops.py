@@ -359,6 +359,15 @@ def vit_bf16_active(dim, num_heads, mlp_dim=None):
     return bool(VIT_BF16 and MFMA_BF16 and not MFMA_F32X3 and vit_bf16_covers(dim, num_heads, mlp_dim))
 
 
+def vit_train_covers(dim, num_heads):
+    """Whether the training forward of the SAM ViT encoder (sgv3d_amd/vit_train.py) takes a Block of this shape: head_dim 32, 64 or
+    80 (sgv3d_vit_attention_backward) and 16-byte f32 rows (dim a multiple of 4).  An uncovered shape raises before any launch."""
+    dim, num_heads = int(dim), int(num_heads)
+    if dim <= 0 or num_heads <= 0 or dim % num_heads or dim % 4:
+        return False
+    return dim // num_heads in (32, 64, 80)
+
+
 def dice_covers(mode, num_classes):
     """Whether losses.DiceLoss takes this mode and class count: 'multiclass' keeps one pixel's classes in a thread's registers
     (csrc/dice_loss.hip), which covers 2..32 classes (SGV3D has 7); 'binary' and 'multilabel' walk the classes and take any
