@@ -339,3 +339,20 @@ def stream_handle(device=None):
 def ptr(t):
     """Device pointer of a tensor or None."""
     return None if t is None else t.data_ptr()
+
+
+REL_POS_NOT_BUILT = "interpolated relative-position tables are not built"
+
+
+def vit_attn_desc(qkv, num_heads, window, pad_qkv=None, rel_pos_h=None, rel_pos_w=None):
+    """The ``VitAttnDesc`` of qkv [B, H, W, 3 * heads * head_dim] with ``window`` = (win_h, win_w), after checking the shapes of
+    the tables and of ``pad_qkv``.  Dtype and contiguity are each caller's own to assert."""
+    assert qkv.dim() == 4 and qkv.shape[-1] % (3 * num_heads) == 0
+    b, h, w, c3 = (int(s) for s in qkv.shape)
+    d = VitAttnDesc(b, h, w, int(num_heads), c3 // 3 // int(num_heads), int(window[0]), int(window[1]))
+    for name, tab, win in (("rel_pos_h", rel_pos_h, d.win_h), ("rel_pos_w", rel_pos_w, d.win_w)):
+        if tab is not None and tuple(tab.shape) != (2 * win - 1, d.head_dim):
+            raise SGV3DError(f"{name} has shape {tuple(tab.shape)}, the window needs {(2 * win - 1, d.head_dim)}: {REL_POS_NOT_BUILT}")
+    if pad_qkv is not None:
+        assert pad_qkv.numel() == c3
+    return d

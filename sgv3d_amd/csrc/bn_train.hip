@@ -279,8 +279,6 @@ int stream_blocks(long long total, int c4n) {
     return (int)((b + step - 1) / step * step);
 }
 
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 size_t partial_bytes(int) { return (size_t)kMaxBlocks * 64 * 2 * sizeof(double); }
 
 }  // namespace

@@ -14,6 +14,7 @@ int check_launch(const char *what);
 
 static inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }   // null passes
 
 constexpr int kWave = 64;  // gfx950 wavefront
 

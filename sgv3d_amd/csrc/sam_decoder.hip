@@ -30,8 +30,6 @@ constexpr int kSmall = 16;     // the small side of sgv3d_sam_attention: at most
 constexpr int kChunk = 256;    // keys per workgroup of the few-queries kernel: one per thread
 constexpr int kPrecision = 22; // Pillow's PRECISION_BITS for 8-bit images
 
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ------------------------------------------------------------------------------------------------
 // attention with one small side
 // ------------------------------------------------------------------------------------------------

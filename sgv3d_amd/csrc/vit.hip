@@ -1,28 +1,17 @@
 // SAM's ViT image encoder (layers/backbones/sam_encoder.py of the reference), the parts that are not a convolution:
 // windowed / global attention with decomposed relative position (one flash-style launch on the f32 MFMA), LayerNorm over
 // the channels of an NHWC map, exact GELU, the input normalise + pad, and the crop + bilinear resize behind the neck.
-// gfx950 only.  Vector stores only, no float atomics: every kernel is repeatable bit for bit.
-#include <math.h>
-
-#include "common.hpp"
+// What the bf16 forms (csrc/vit_bf16.hip) and the adjoints (csrc/vit_grad.hip) must share with these kernels bit for bit is
+// defined once, in csrc/vit_common.hpp.  gfx950 only.  Vector stores only, no float atomics: every kernel is repeatable bit for bit.
+#include "vit_common.hpp"
 
 using namespace sgv3d;
 
-namespace sgv3d {
-int vit_attention_impl(const sgv3d_vit_attn_desc *desc, const float *qkv, const float *pad_qkv, const float *rel_pos_h,
-                       const float *rel_pos_w, float *out, float *lse, void *stream);
-}
-
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kBlock = 256;
 constexpr int kQT = 64;  // queries per workgroup: 16 per wave
 constexpr int kKT = 64;  // keys per LDS tile
-
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // ------------------------------------------------------------------------------------------------
 // attention
@@ -43,8 +32,8 @@ static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t
 // 16-byte operand reads of both are conflict-free in the lane groups the LDS serves them in.  The next tile is loaded into
 // registers after QK^T and written to LDS behind the barrier.  T_h = q rel_pos_h^T and T_w = q rel_pos_w^T are formed once
 // per workgroup on the MFMA (table rows as the A operand) and kept in LDS as [query][kh] and [query][kw].
-// Workgroups are renumbered so that each of the 8 XCDs, which take consecutive workgroup ids in turn, walks a contiguous
-// run of (image, head, window, query tile): the query tiles that share a head's K and V then share an L2.
+// Workgroups are renumbered over the 8 XCDs (decode_workgroup); the P V loop and the store of O^T are accum_rows and store_rows,
+// which the backward uses as well.
 struct AttnParams {
     int B, H, W, nH, win_h, win_w, nwy, nwx, T, nqt, th_ld, tw_ld;
     float scale, inv_win_w;
@@ -66,8 +55,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HD <= 64
     constexpr int NC = HD / 16;  // 16-byte operand reads per key row of QK^T (four k-steps each)
     constexpr int NS = HD / 4;   // k-steps of QK^T
     constexpr int NJ = HD / 16;  // accumulators of O^T
-    constexpr int N4 = NJ / 4, N2 = (NJ % 4) / 2, N1 = NJ % 2;   // ... fed four, two and one at a time
-    constexpr int D2 = 64 * N4, D1 = D2 + 32 * N2;               // where the 8- and 4-byte parts of the head dimension begin
     constexpr int NL = HD / 16;  // float4 per thread, tensor and tile
     constexpr int C4 = HD / 4;   // float4 per key row
     extern __shared__ __align__(16) float lds[];
@@ -77,34 +64,22 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HD <= 64
     float *Tw = Th + kQT * p.th_ld;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lq = lane & 15, g = lane >> 4;
-    int bid = blockIdx.x;
-    {
-        const int per_xcd = gridDim.x / 8;
-        if (bid < 8 * per_xcd) bid = (bid & 7) * per_xcd + (bid >> 3);     // (the last gridDim.x % 8 ids stay)
-    }
-    const int qt = bid % p.nqt;
-    bid /= p.nqt;
-    const int wx = bid % p.nwx;
-    bid /= p.nwx;
-    const int wy = bid % p.nwy;
-    bid /= p.nwy;
-    const int head = bid % p.nH;
-    const int b = bid / p.nH;
+    const Window wg = decode_workgroup(p);
+    const int head = wg.head;
     const int C = p.nH * HD;
-    const int h0 = wy * p.win_h, w0 = wx * p.win_w;
     const bool rel = p.rh != nullptr;
 
     // q, k, v of window token t (< T): the map's row, or the padding token's (null: zeros)
     auto token = [&](int t) -> const float * {
-        const int kh = (int)(((float)t + 0.5f) * p.inv_win_w), kw = t - kh * p.win_w;     // t / win_w, see below
-        const int h = h0 + kh, w = w0 + kw;
-        if (h < p.H && w < p.W) return p.qkv + ((size_t)((size_t)b * p.H + h) * p.W + w) * (size_t)(3 * C) + head * HD;
+        const int kh = slot_row(t, p.inv_win_w);
+        long long pix;
+        if (wg.pixel(p, kh, t - kh * p.win_w, pix)) return p.qkv + pix * (3 * C) + head * HD;
         return p.pad ? p.pad + head * HD : nullptr;
     };
 
     // this lane's query: q[4 c + i] = Q[16 c + 4 g + i]
     const int myq = wave * 16 + lq;
-    int tq = qt * kQT + myq;
+    int tq = wg.qt * kQT + myq;
     const bool q_live = tq < p.T;
     tq = q_live ? tq : p.T - 1;
     const int qh = tq / p.win_w, qw = tq - qh * p.win_w;
@@ -219,10 +194,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HD <= 64
                 const int t = tile * kKT + sub * 16 + 4 * g + r;
                 float s = S[sub][r];
                 if (rel) {
-                    // kh = t / win_w without the integer division: exact for t < 128 * win_w, win_w <= 128 (every case is
-                    // enumerated in tests/test_sam_encoder_cpu.py); a slot past T reads a valid entry and is masked below
+                    // a slot past T reads a valid entry and is masked below
                     const int tc = last ? min(t, p.T - 1) : t;
-                    const int kh = (int)(((float)tc + 0.5f) * p.inv_win_w), kw = tc - kh * p.win_w;
+                    const int kh = slot_row(tc, p.inv_win_w), kw = tc - kh * p.win_w;
                     s += th[kh] + tw[kw];
                 }
                 if (last && t >= p.T) s = -INFINITY;     // a key past the window: masked, not a zero logit
@@ -246,53 +220,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(HD <= 64
             }
         m = m_new;
 
-#pragma unroll
-        for (int sub = 0; sub < 4; ++sub)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float *vrow = vbase + (sub * 16 + r) * LDV;
-                const float pk = S[sub][r];
-#pragma unroll
-                for (int c = 0; c < N4; ++c) {
-                    const f32x4 vf = *reinterpret_cast<const f32x4 *>(vrow + 64 * c + 4 * lq);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) O[4 * c + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[i], pk, O[4 * c + i], 0, 0, 0);
-                }
-                if (N2) {
-                    const f32x2 vf = *reinterpret_cast<const f32x2 *>(vrow + D2 + 2 * lq);
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-                        O[4 * N4 + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[i], pk, O[4 * N4 + i], 0, 0, 0);
-                }
-                if (N1) O[NJ - 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(vrow[D1 + lq], pk, O[NJ - 1], 0, 0, 0);
-            }
+        accum_rows<HD, LDV>(O, vbase, S, lq);      // O^T += V^T P^T
     }
 
     l += __shfl_xor(l, 16);
     l += __shfl_xor(l, 32);
-    const int oh = h0 + qh, ow = w0 + qw;
+    const int oh = wg.h0 + qh, ow = wg.w0 + qw;
     if (q_live && oh < p.H && ow < p.W) {
-        if (LSE && g == 0) p.lse[(((size_t)b * p.nH + head) * p.H + oh) * p.W + ow] = m + logf(l);
-        // row 4 g + r of accumulator 4 c + i is d = 64 c + 4 (4 g + r) + i: sixteen consecutive floats per lane and c
-        float *dst = p.out + ((size_t)((size_t)b * p.H + oh) * p.W + ow) * (size_t)C + head * HD;
-#pragma unroll
-        for (int c = 0; c < N4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const f32x4 o = {O[4 * c][r] / l, O[4 * c + 1][r] / l, O[4 * c + 2][r] / l, O[4 * c + 3][r] / l};
-                *reinterpret_cast<f32x4 *>(dst + 64 * c + 16 * g + 4 * r) = o;
-            }
-        if (N2) {      // d = D2 + 2 (4 g + r) + i
-#pragma unroll
-            for (int r = 0; r < 4; r += 2) {
-                const f32x4 o = {O[4 * N4][r] / l, O[4 * N4 + 1][r] / l, O[4 * N4][r + 1] / l, O[4 * N4 + 1][r + 1] / l};
-                *reinterpret_cast<f32x4 *>(dst + D2 + 8 * g + 2 * r) = o;
-            }
-        }
-        if (N1) {      // d = D1 + 4 g + r
-            const f32x4 o = {O[NJ - 1][0] / l, O[NJ - 1][1] / l, O[NJ - 1][2] / l, O[NJ - 1][3] / l};
-            *reinterpret_cast<f32x4 *>(dst + D1 + 4 * g) = o;
-        }
+        if (LSE && g == 0) p.lse[(((size_t)wg.b * p.nH + head) * p.H + oh) * p.W + ow] = m + logf(l);
+        float *dst = p.out + ((size_t)((size_t)wg.b * p.H + oh) * p.W + ow) * (size_t)C + head * HD;
+        store_rows<HD>(dst, O, g, [l](float o) { return o / l; });
     }
 }
 
@@ -312,17 +249,8 @@ int launch_attention(const AttnParams &p, int blocks, size_t lds_bytes, hipStrea
 }
 
 // ------------------------------------------------------------------------------------------------
-// LayerNorm: one wave per row
+// LayerNorm: one wave per row (ln_row_stats, ln_xhat)
 // ------------------------------------------------------------------------------------------------
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// Two passes, never E[x^2] - E[x]^2.  The sums are carried in f64: the test's bar is relative to |x_hat| element by element, and
-// a mean rounded to f32 is off by up to half an ulp OF THE MEAN -- for a row that sits at 1e4 with unit spread that alone is
-// 5e-4 on every x_hat, whatever its size.  With the f64 mean, x - mean is rounded once, relative to itself.
 __global__ __launch_bounds__(kBlock) void layernorm_kernel(long long rows, int c4, const f32x4 *x, const f32x4 *__restrict__ weight,
                                                            const f32x4 *__restrict__ bias, float eps, f32x4 *y) {
     const int lane = threadIdx.x & 63;
@@ -330,38 +258,19 @@ __global__ __launch_bounds__(kBlock) void layernorm_kernel(long long rows, int c
     if (row >= rows) return;
     const f32x4 *xr = x + row * c4;
     f32x4 *yr = y + row * c4;
-    const double inv_c = 1.0 / (4.0 * (double)c4);
-    double s = 0.0;
-    for (int i = lane; i < c4; i += 64) {
-        const f32x4 v = xr[i];
-        s += ((double)v[0] + (double)v[1]) + ((double)v[2] + (double)v[3]);
-    }
-    const double mean = wave_sum(s) * inv_c;
-    double sq = 0.0;
-    for (int i = lane; i < c4; i += 64) {
-        const f32x4 v = xr[i];
-        const double e0 = (double)v[0] - mean, e1 = (double)v[1] - mean, e2 = (double)v[2] - mean, e3 = (double)v[3] - mean;
-        sq += (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
-    }
-    const float rstd = (float)(1.0 / sqrt(wave_sum(sq) * inv_c + (double)eps));
+    const LnStats st = ln_row_stats(xr, c4, lane, eps);
     for (int i = lane; i < c4; i += 64) {
         const f32x4 v = xr[i], w = weight[i], bb = bias[i];
         f32x4 o;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = (float)((double)v[k] - mean) * rstd * w[k] + bb[k];
+        for (int k = 0; k < 4; ++k) o[k] = ln_xhat(v[k], st) * w[k] + bb[k];
         yr[i] = o;
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// GELU (erf form).  For x < 0, 1 + erf(z) is written erfc(-z): no cancellation in the left tail.
+// GELU (erf form, gelu1)
 // ------------------------------------------------------------------------------------------------
-__device__ inline float gelu1(float x) {
-    const float z = x * 0.70710678118654752440f;
-    const float t = x < 0.f ? erfcf(-z) : 1.0f + erff(z);
-    return 0.5f * x * t;
-}
-
 __global__ __launch_bounds__(kBlock) void gelu_kernel(long long n4, int tail, const float *x, float *y) {
     const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (i < n4) {
@@ -428,31 +337,19 @@ __global__ __launch_bounds__(kBlock) void resize_bilinear_kernel(int B, int h, i
 // sgv3d_vit_attention, and with `lse` sgv3d_vit_attention_lse (csrc/vit_grad.hip): one body, so `out` has the same bits in both
 int sgv3d::vit_attention_impl(const sgv3d_vit_attn_desc *desc, const float *qkv, const float *pad_qkv, const float *rel_pos_h,
                               const float *rel_pos_w, float *out, float *lse, void *stream) {
-    SGV3D_REQUIRE(desc, "vit_attention: null descriptor");
+    const int rc = check_attn_desc("vit_attention", desc, 4);
+    if (rc != SGV3D_OK) return rc;
     const sgv3d_vit_attn_desc &d = *desc;
-    SGV3D_REQUIRE(d.batch > 0 && d.height > 0 && d.width > 0 && d.heads > 0 && d.head_dim > 0 && d.win_h > 0 && d.win_w > 0,
-                  "vit_attention: zero or negative dimension (batch %d, map %d x %d, heads %d, head_dim %d, window %d x %d)", d.batch,
-                  d.height, d.width, d.heads, d.head_dim, d.win_h, d.win_w);
-    SGV3D_REQUIRE((long long)d.heads * d.head_dim % 4 == 0, "vit_attention: heads * head_dim = %lld is not a multiple of 4", (long long)d.heads * d.head_dim);
-    SGV3D_REQUIRE(d.head_dim == 32 || d.head_dim == 64 || d.head_dim == 80, "vit_attention: head_dim %d is not one of 32, 64, 80",
-                  d.head_dim);
-    SGV3D_REQUIRE(d.win_h <= 128 && d.win_w <= 128, "vit_attention: window %d x %d exceeds 128", d.win_h, d.win_w);
     SGV3D_REQUIRE((rel_pos_h == nullptr) == (rel_pos_w == nullptr),
                   "vit_attention: rel_pos_h and rel_pos_w must be given together or not at all");
     SGV3D_REQUIRE(qkv && out, "vit_attention: null qkv or out");
     SGV3D_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(pad_qkv), "vit_attention: qkv, pad_qkv and out must be 16-byte aligned");
-    const long long channels = (long long)d.heads * d.head_dim;
-    SGV3D_REQUIRE(3 * channels < (1LL << 24), "vit_attention: heads * head_dim too large");
     AttnParams p;
-    p.B = d.batch, p.H = d.height, p.W = d.width, p.nH = d.heads, p.win_h = d.win_h, p.win_w = d.win_w;
-    p.nwy = cdiv(d.height, d.win_h), p.nwx = cdiv(d.width, d.win_w);
-    p.T = d.win_h * d.win_w;
+    fill_window(p, d);
     p.nqt = cdiv(p.T, kQT);
     const bool rel = rel_pos_h != nullptr;
-    p.th_ld = rel ? (d.win_h | 1) : 0;      // odd rows: the four lanes of a query and its 15 neighbours spread over the banks
-    p.tw_ld = rel ? (d.win_w | 1) : 0;
-    p.scale = 1.0f / sqrtf((float)d.head_dim);
-    p.inv_win_w = 1.0f / (float)d.win_w;
+    p.th_ld = odd_ld(rel, d.win_h), p.tw_ld = odd_ld(rel, d.win_w);
+    p.scale = softmax_scale(d.head_dim);
     p.qkv = qkv, p.pad = pad_qkv, p.rh = rel_pos_h, p.rw = rel_pos_w, p.out = out, p.lse = lse;
     const long long blocks = (long long)d.batch * d.heads * p.nwy * p.nwx * p.nqt;
     SGV3D_REQUIRE(blocks < (1LL << 31), "vit_attention: too many workgroups");

@@ -1,16 +1,15 @@
 // SAM's ViT image encoder in bf16 mode (hip_ops.VIT_BF16): the attention launch on v_mfma_f32_16x16x32_bf16 with bf16 tensors in
 // HBM, LayerNorm with a bf16 result and GELU on bf16 tensors.  The f32 forms are csrc/vit.hip; the semantics (windows indexed in
 // the un-partitioned map, the qkv bias as the padding tokens, the unscaled q in the relative-position terms) are the same.
+// The descriptor checks, the window geometry, the LayerNorm row statistics and the GELU formula are the f32 forms' own, from
+// csrc/vit_common.hpp; the attention inner loop has other MFMA operands and is this file's.
 // gfx950 only.  Vector stores only, no atomics: every kernel is repeatable bit for bit.
-#include <math.h>
-
-#include "common.hpp"
+#include "vit_common.hpp"
 
 using namespace sgv3d;
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -18,8 +17,6 @@ typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kBlock = 256;
 constexpr int kKT = 64;  // keys per LDS tile: two k-steps of 32 keys for P V, four 16-key sub-tiles for Q K^T
-
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 __device__ __forceinline__ bf16x8 zero8() {
     bf16x8 z;
@@ -71,7 +68,7 @@ __device__ __forceinline__ bf16x8 tr_read8(const unsigned char *lds, int off, in
 // Both are double-buffered: the next tile is loaded into registers after Q K^T and written to the other buffer after P V, one
 // barrier per tile.  T_h = q rel_pos_h^T and T_w = q rel_pos_w^T (bf16 operands, f32 sums) are formed once per workgroup on the
 // MFMA and kept in LDS as f32 [query][kh] and [query][kw].  The last tile of a window skips its second 32-key block when no key
-// lives there.  Workgroups are renumbered over the 8 XCDs as in csrc/vit.hip.
+// lives there.  Workgroups are renumbered over the 8 XCDs (decode_workgroup).
 struct AttnParams {
     int B, H, W, nH, win_h, win_w, nwy, nwx, T, nqt, th_ld, tw_ld;
     float scale2, inv_win_w;      // scale2 = head_dim^-0.5 log2(e): the logits are kept in units of log2
@@ -107,30 +104,17 @@ __global__ __launch_bounds__(kBlock) void vit_attention_bf16_kernel(AttnParams p
     float *Tw = Th + QT * p.th_ld;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lq = lane & 15, g = lane >> 4;
-    int bid = blockIdx.x;
-    {
-        const int per_xcd = gridDim.x / 8;
-        if (bid < 8 * per_xcd) bid = (bid & 7) * per_xcd + (bid >> 3);     // (the last gridDim.x % 8 ids stay)
-    }
-    const int qt = bid % p.nqt;
-    bid /= p.nqt;
-    const int wx = bid % p.nwx;
-    bid /= p.nwx;
-    const int wy = bid % p.nwy;
-    bid /= p.nwy;
-    const int head = bid % p.nH;
-    const int b = bid / p.nH;
+    const Window wg = decode_workgroup(p);
+    const int head = wg.head;
     const int C = p.nH * HD;
-    const int h0 = wy * p.win_h, w0 = wx * p.win_w;
     const bool rel = p.rh != nullptr;
 
     // eight consecutive d of q (which = 0), k (1) or v (2) of window token t (< T): the map's, or the padding token's (null: zeros)
     auto load8 = [&](int t, int which, int d0) -> bf16x8 {
-        const int kh = (int)(((float)t + 0.5f) * p.inv_win_w), kw = t - kh * p.win_w;     // t / win_w, as in csrc/vit.hip
-        const int h = h0 + kh, w = w0 + kw;
+        const int kh = slot_row(t, p.inv_win_w);
         const int col = which * C + head * HD + d0;
-        if (h < p.H && w < p.W)
-            return *reinterpret_cast<const bf16x8 *>(p.qkv + ((size_t)((size_t)b * p.H + h) * p.W + w) * (size_t)(3 * C) + col);
+        long long pix;
+        if (wg.pixel(p, kh, t - kh * p.win_w, pix)) return *reinterpret_cast<const bf16x8 *>(p.qkv + pix * (3 * C) + col);
         if (p.pad) return cvt8(p.pad + col);
         return zero8();
     };
@@ -140,7 +124,7 @@ __global__ __launch_bounds__(kBlock) void vit_attention_bf16_kernel(AttnParams p
     bf16x8 qf[QW][NK];
 #pragma unroll
     for (int qb = 0; qb < QW; ++qb) {
-        int tq = qt * QT + (wave * QW + qb) * 16 + lq;
+        int tq = wg.qt * QT + (wave * QW + qb) * 16 + lq;
         q_live[qb] = tq < p.T;
         tq = q_live[qb] ? tq : p.T - 1;
         qh[qb] = tq / p.win_w;
@@ -275,7 +259,7 @@ __global__ __launch_bounds__(kBlock) void vit_attention_bf16_kernel(AttnParams p
             if (rel) {
                 if (VEC) {
                     const int tc = min(t0, p.T - 4);
-                    const int kh = (int)(((float)tc + 0.5f) * p.inv_win_w), kw = tc - kh * p.win_w;
+                    const int kh = slot_row(tc, p.inv_win_w), kw = tc - kh * p.win_w;
 #pragma unroll
                     for (int qb = 0; qb < QW; ++qb) {
                         const float a = th[qb][kh];
@@ -286,7 +270,7 @@ __global__ __launch_bounds__(kBlock) void vit_attention_bf16_kernel(AttnParams p
                 } else {
                     // (kh, kw) of four consecutive slots: one division, then steps
                     const int tc = min(t0, p.T - 1);
-                    int kh = (int)(((float)tc + 0.5f) * p.inv_win_w), kw = tc - kh * p.win_w;
+                    int kh = slot_row(tc, p.inv_win_w), kw = tc - kh * p.win_w;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
 #pragma unroll
@@ -354,10 +338,10 @@ __global__ __launch_bounds__(kBlock) void vit_attention_bf16_kernel(AttnParams p
 #pragma unroll
     for (int qb = 0; qb < QW; ++qb) {
         const float sum = L[qb][0];
-        const int oh = h0 + qh[qb], ow = w0 + qw[qb];
+        const int oh = wg.h0 + qh[qb], ow = wg.w0 + qw[qb];
         if (q_live[qb] && oh < p.H && ow < p.W) {
             // row 4 g + r of accumulator db is d = 16 db + 4 g + r: four consecutive bf16 per lane and db
-            __bf16 *dst = p.out + ((size_t)((size_t)b * p.H + oh) * p.W + ow) * (size_t)C + head * HD + 4 * g;
+            __bf16 *dst = p.out + ((size_t)((size_t)wg.b * p.H + oh) * p.W + ow) * (size_t)C + head * HD + 4 * g;
 #pragma unroll
             for (int db = 0; db < ND; ++db) {
                 bf16x4 o;
@@ -385,14 +369,8 @@ int launch_attention_hd(const AttnParams &p, bool wide, bool vec, int blocks, si
 }
 
 // ------------------------------------------------------------------------------------------------
-// LayerNorm with a bf16 result: the arithmetic of csrc/vit.hip's layernorm_kernel statement by statement, one more rounding
+// LayerNorm with a bf16 result: layernorm_kernel of csrc/vit.hip (ln_row_stats, ln_xhat) and one more rounding
 // ------------------------------------------------------------------------------------------------
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __global__ __launch_bounds__(kBlock) void layernorm_bf16out_kernel(long long rows, int c4, const f32x4 *x, const f32x4 *__restrict__ weight,
                                                                    const f32x4 *__restrict__ bias, float eps, bf16x4 *y) {
     const int lane = threadIdx.x & 63;
@@ -400,25 +378,12 @@ __global__ __launch_bounds__(kBlock) void layernorm_bf16out_kernel(long long row
     if (row >= rows) return;
     const f32x4 *xr = x + row * c4;
     bf16x4 *yr = y + row * c4;
-    const double inv_c = 1.0 / (4.0 * (double)c4);
-    double s = 0.0;
-    for (int i = lane; i < c4; i += 64) {
-        const f32x4 v = xr[i];
-        s += ((double)v[0] + (double)v[1]) + ((double)v[2] + (double)v[3]);
-    }
-    const double mean = wave_sum(s) * inv_c;
-    double sq = 0.0;
-    for (int i = lane; i < c4; i += 64) {
-        const f32x4 v = xr[i];
-        const double e0 = (double)v[0] - mean, e1 = (double)v[1] - mean, e2 = (double)v[2] - mean, e3 = (double)v[3] - mean;
-        sq += (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
-    }
-    const float rstd = (float)(1.0 / sqrt(wave_sum(sq) * inv_c + (double)eps));
+    const LnStats st = ln_row_stats(xr, c4, lane, eps);
     for (int i = lane; i < c4; i += 64) {
         const f32x4 v = xr[i], w = weight[i], bb = bias[i];
         f32x4 o;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = (float)((double)v[k] - mean) * rstd * w[k] + bb[k];
+        for (int k = 0; k < 4; ++k) o[k] = ln_xhat(v[k], st) * w[k] + bb[k];
         bf16x4 ob;
 #pragma unroll
         for (int k = 0; k < 4; ++k) ob[k] = (__bf16)o[k];
@@ -427,14 +392,8 @@ __global__ __launch_bounds__(kBlock) void layernorm_bf16out_kernel(long long row
 }
 
 // ------------------------------------------------------------------------------------------------
-// GELU on bf16 tensors: csrc/vit.hip's f32 formula on the widened value, rounded once
+// GELU on bf16 tensors: the f32 formula (gelu1) on the widened value, rounded once
 // ------------------------------------------------------------------------------------------------
-__device__ inline float gelu1(float x) {
-    const float z = x * 0.70710678118654752440f;
-    const float t = x < 0.f ? erfcf(-z) : 1.0f + erff(z);
-    return 0.5f * x * t;
-}
-
 __global__ __launch_bounds__(kBlock) void gelu_bf16_kernel(long long n8, int tail, const __bf16 *x, __bf16 *y) {
     const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
     if (i < n8) {
@@ -451,33 +410,21 @@ __global__ __launch_bounds__(kBlock) void gelu_bf16_kernel(long long n8, int tai
 
 extern "C" int sgv3d_vit_attention_bf16(const sgv3d_vit_attn_desc *desc, const void *qkv, const float *pad_qkv, const float *rel_pos_h,
                                         const float *rel_pos_w, void *out, void *stream) {
-    SGV3D_REQUIRE(desc, "vit_attention_bf16: null descriptor");
+    const int rc = check_attn_desc("vit_attention_bf16", desc, 8);
+    if (rc != SGV3D_OK) return rc;
     const sgv3d_vit_attn_desc &d = *desc;
-    SGV3D_REQUIRE(d.batch > 0 && d.height > 0 && d.width > 0 && d.heads > 0 && d.head_dim > 0 && d.win_h > 0 && d.win_w > 0,
-                  "vit_attention_bf16: zero or negative dimension (batch %d, map %d x %d, heads %d, head_dim %d, window %d x %d)", d.batch,
-                  d.height, d.width, d.heads, d.head_dim, d.win_h, d.win_w);
-    SGV3D_REQUIRE((long long)d.heads * d.head_dim % 8 == 0, "vit_attention_bf16: heads * head_dim = %lld is not a multiple of 8",
-                  (long long)d.heads * d.head_dim);
-    SGV3D_REQUIRE(d.head_dim == 32 || d.head_dim == 64 || d.head_dim == 80, "vit_attention_bf16: head_dim %d is not one of 32, 64, 80",
-                  d.head_dim);
-    SGV3D_REQUIRE(d.win_h <= 128 && d.win_w <= 128, "vit_attention_bf16: window %d x %d exceeds 128", d.win_h, d.win_w);
     SGV3D_REQUIRE((rel_pos_h == nullptr) == (rel_pos_w == nullptr),
                   "vit_attention_bf16: rel_pos_h and rel_pos_w must be given together or not at all");
     SGV3D_REQUIRE(qkv && out, "vit_attention_bf16: null qkv or out");
     SGV3D_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(pad_qkv) && aligned16(rel_pos_h) && aligned16(rel_pos_w),
                   "vit_attention_bf16: qkv, pad_qkv, rel_pos_h, rel_pos_w and out must be 16-byte aligned");
-    const long long channels = (long long)d.heads * d.head_dim;
-    SGV3D_REQUIRE(3 * channels < (1LL << 24), "vit_attention_bf16: heads * head_dim too large");
     AttnParams p;
-    p.B = d.batch, p.H = d.height, p.W = d.width, p.nH = d.heads, p.win_h = d.win_h, p.win_w = d.win_w;
-    p.nwy = cdiv(d.height, d.win_h), p.nwx = cdiv(d.width, d.win_w);
-    p.T = d.win_h * d.win_w;
+    fill_window(p, d);
     const bool rel = rel_pos_h != nullptr;
     const bool vec = rel && d.win_w % 4 == 0;      // 16-byte T_w reads: rows of win_w + 4 floats
-    p.th_ld = rel ? (d.win_h | 1) : 0;      // odd rows: the four lanes of a query and its 15 neighbours spread over the banks
-    p.tw_ld = rel ? (vec ? d.win_w + 4 : (d.win_w | 1)) : 0;
-    p.scale2 = 1.0f / sqrtf((float)d.head_dim) * kLog2e;
-    p.inv_win_w = 1.0f / (float)d.win_w;
+    p.th_ld = odd_ld(rel, d.win_h);
+    p.tw_ld = vec ? d.win_w + 4 : odd_ld(rel, d.win_w);
+    p.scale2 = softmax_scale(d.head_dim) * kLog2e;
     p.qkv = static_cast<const __bf16 *>(qkv), p.pad = pad_qkv, p.rh = rel_pos_h, p.rw = rel_pos_w, p.out = static_cast<__bf16 *>(out);
     const size_t kv_bytes = d.head_dim == 32 ? AttnGeom<32>::kv_bytes : d.head_dim == 64 ? AttnGeom<64>::kv_bytes : AttnGeom<80>::kv_bytes;
     const size_t t_bytes = sizeof(float) * (size_t)(p.th_ld + p.tw_ld);      // per query

@@ -1,28 +1,18 @@
 // Training adjoints of SAM's ViT image encoder (csrc/vit.hip): the attention launch with windows, padding tokens and the decomposed
 // relative position, LayerNorm, the exact GELU and the crop + bilinear resize.  gfx950 only.  Vector stores only, no float atomics,
 // a fixed summation order everywhere: every entry is repeatable bit for bit and graph-capturable (no host wait, no allocation).
-#include <math.h>
-
-#include "common.hpp"
+// What must repeat the forward bit for bit (the window geometry, the LayerNorm row statistics, the erf term of GELU, the f32 MFMA
+// operand code) is the forward's own definition, from csrc/vit_common.hpp.
+#include "vit_common.hpp"
 
 using namespace sgv3d;
 
-namespace sgv3d {
-// csrc/vit.hip: sgv3d_vit_attention with an optional lse output (the same kernel body, the same bits of `out`)
-int vit_attention_impl(const sgv3d_vit_attn_desc *desc, const float *qkv, const float *pad_qkv, const float *rel_pos_h,
-                       const float *rel_pos_w, float *out, float *lse, void *stream);
-}  // namespace sgv3d
-
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kBlock = 256;
 constexpr int kTile = 64;     // owned rows per workgroup (16 per wave) and streamed rows per LDS tile
 constexpr int kLnChunk = 32;  // rows per partial of the LayerNorm weight / bias gradient
 
-static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline long long up4(long long v) { return (v + 3) & ~3LL; }
 // two ranges of `bytes` bytes each
 static inline bool overlaps(const void *a, const void *b, unsigned long long bytes) {
@@ -80,32 +70,11 @@ struct BwdParams {
     long long G;
 };
 
-struct Group {
-    int b, head, h0, w0;
-};
-
-__device__ inline Group decode_group(const BwdParams &p, long long g) {
-    Group r;
-    const int wx = (int)(g % p.nwx);
-    g /= p.nwx;
-    const int wy = (int)(g % p.nwy);
-    g /= p.nwy;
-    r.head = (int)(g % p.nH);
-    r.b = (int)(g / p.nH);
-    r.h0 = wy * p.win_h, r.w0 = wx * p.win_w;
-    return r;
-}
-
-// t / win_w without the integer division, as the forward does it: exact for t < 128 * win_w, win_w <= 128 (every case is enumerated
-// in tests/test_sam_encoder_cpu.py)
-__device__ inline int slot_row(const BwdParams &p, int t) { return (int)(((float)t + 0.5f) * p.inv_win_w); }
-
 // pixel index ((b * H + h) * W + w) of window slot t (< T), or -1 for a padding slot
-__device__ inline long long slot_pixel(const BwdParams &p, const Group &gr, int t) {
-    const int kh = t / p.win_w, kw = t - kh * p.win_w;
-    const int h = gr.h0 + kh, w = gr.w0 + kw;
-    if (h < p.H && w < p.W) return ((long long)gr.b * p.H + h) * p.W + w;
-    return -1;
+__device__ inline long long slot_pixel(const BwdParams &p, const Window &gr, int t) {
+    const int kh = t / p.win_w;
+    long long pix;
+    return gr.pixel(p, kh, t - kh * p.win_w, pix) ? pix : -1;
 }
 
 // One workgroup of 64 threads per (group, slot): the slot's lse and delta and its row of th / tw.
@@ -113,7 +82,7 @@ __global__ __launch_bounds__(64) void attn_bwd_prep_kernel(BwdParams p) {
     const long long bid = blockIdx.x;
     const long long g = bid / p.Tp;
     const int i = (int)(bid - g * p.Tp);
-    const Group gr = decode_group(p, g);
+    const Window gr = decode_window(p, g);
     const int HD = p.HD, C = p.nH * HD;
     const long long pix = i < p.T ? slot_pixel(p, gr, i) : -1;
     const bool rel = p.rh != nullptr;
@@ -169,8 +138,6 @@ template <int HD, bool KEYS>
 __global__ __launch_bounds__(kBlock) void attn_bwd_kernel(BwdParams p) {
     constexpr int LD = BwdGeom<HD>::LD;
     constexpr int NC = HD / 16, NS = HD / 4, NJ = HD / 16;
-    constexpr int N4 = NJ / 4, N2 = (NJ % 4) / 2, N1 = NJ % 2;
-    constexpr int D2 = 64 * N4, D1 = D2 + 32 * N2;
     constexpr int NL = HD / 16, C4 = HD / 4;
     extern __shared__ __align__(16) float lds[];
     float *Xs = lds;
@@ -181,7 +148,7 @@ __global__ __launch_bounds__(kBlock) void attn_bwd_kernel(BwdParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lq = lane & 15, g = lane >> 4;
     const long long grp = blockIdx.x / p.nt;
     const int ot = (int)(blockIdx.x - grp * p.nt);
-    const Group gr = decode_group(p, grp);
+    const Window gr = decode_window(p, grp);
     const int C = p.nH * HD;
     const bool rel = p.rh != nullptr;
     const float *lse_w = p.lse_w + grp * p.Tp, *delta_w = p.delta_w + grp * p.Tp;
@@ -254,50 +221,10 @@ __global__ __launch_bounds__(kBlock) void attn_bwd_kernel(BwdParams p) {
         }
     };
     // acc^T[d][owned] += sum over the tile's rows of M[row][d] * Wt[row][owned]
-    auto accum = [&](f32x4(&acc)[NJ], const float *M, const f32x4(&Wt)[4]) {
-        const float *mbase = M + 4 * g * LD;
-#pragma unroll
-        for (int sub = 0; sub < 4; ++sub)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const float *mrow = mbase + (sub * 16 + r) * LD;
-                const float wk = Wt[sub][r];
-#pragma unroll
-                for (int c = 0; c < N4; ++c) {
-                    const f32x4 mf = *reinterpret_cast<const f32x4 *>(mrow + 64 * c + 4 * lq);
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[4 * c + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(mf[i], wk, acc[4 * c + i], 0, 0, 0);
-                }
-                if (N2) {
-                    const f32x2 mf = *reinterpret_cast<const f32x2 *>(mrow + D2 + 2 * lq);
-#pragma unroll
-                    for (int i = 0; i < 2; ++i)
-                        acc[4 * N4 + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(mf[i], wk, acc[4 * N4 + i], 0, 0, 0);
-                }
-                if (N1) acc[NJ - 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(mrow[D1 + lq], wk, acc[NJ - 1], 0, 0, 0);
-            }
-    };
+    auto accum = [&](f32x4(&acc)[NJ], const float *M, const f32x4(&Wt)[4]) { accum_rows<HD, LD>(acc, M + 4 * g * LD, Wt, lq); };
     // stage acc^T (times mul) as rows [owned][d] of an LDS tile with row length LD
     auto stage = [&](float *dst_tile, const f32x4(&acc)[NJ], float mul) {
-        float *dst = dst_tile + myrow * LD;
-#pragma unroll
-        for (int c = 0; c < N4; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const f32x4 v = {acc[4 * c][r] * mul, acc[4 * c + 1][r] * mul, acc[4 * c + 2][r] * mul, acc[4 * c + 3][r] * mul};
-                *reinterpret_cast<f32x4 *>(dst + 64 * c + 16 * g + 4 * r) = v;
-            }
-        if (N2) {
-#pragma unroll
-            for (int r = 0; r < 4; r += 2) {
-                const f32x4 v = {acc[4 * N4][r] * mul, acc[4 * N4 + 1][r] * mul, acc[4 * N4][r + 1] * mul, acc[4 * N4 + 1][r + 1] * mul};
-                *reinterpret_cast<f32x4 *>(dst + D2 + 8 * g + 2 * r) = v;
-            }
-        }
-        if (N1) {
-            const f32x4 v = {acc[NJ - 1][0] * mul, acc[NJ - 1][1] * mul, acc[NJ - 1][2] * mul, acc[NJ - 1][3] * mul};
-            *reinterpret_cast<f32x4 *>(dst + D1 + 4 * g) = v;
-        }
+        store_rows<HD>(dst_tile + myrow * LD, acc, g, [mul](float v) { return v * mul; });
     };
 
     f32x4 acc1[NJ], acc2[NJ];     // KEYS: dk^T, dv^T; else dq^T (acc2 unused)
@@ -352,7 +279,7 @@ __global__ __launch_bounds__(kBlock) void attn_bwd_kernel(BwdParams p) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int tc = min(t0 + r, p.T - 1);
-                        const int kh = slot_row(p, tc), kw = tc - kh * p.win_w;
+                        const int kh = slot_row(tc, p.inv_win_w), kw = tc - kh * p.win_w;
                         thv[r] = p.th[(grp * p.Tp + o) * p.win_h + kh];
                         twv[r] = p.tw[(grp * p.Tp + o) * p.win_w + kw];
                     }
@@ -393,7 +320,7 @@ __global__ __launch_bounds__(kBlock) void attn_bwd_kernel(BwdParams p) {
                             for (int r = 0; r < 4; ++r) {
                                 const int t = tile * kTile + sub * 16 + 4 * g + r;
                                 if (t < p.T) {
-                                    const int kh = slot_row(p, t), kw = t - kh * p.win_w;
+                                    const int kh = slot_row(t, p.inv_win_w), kw = t - kh * p.win_w;
                                     if (kh != cur) {
                                         if (cur >= 0) ahrow[cur] += run;
                                         cur = kh, run = 0.f;
@@ -414,7 +341,7 @@ __global__ __launch_bounds__(kBlock) void attn_bwd_kernel(BwdParams p) {
                         for (int r = 0; r < 4; ++r) {
                             const int t = tile * kTile + sub * 16 + 4 * g + r;
                             if (t < p.T) {
-                                const int kh = slot_row(p, t);
+                                const int kh = slot_row(t, p.inv_win_w);
                                 awrow[t - kh * p.win_w] += dP[sub][r];
                             }
                         }
@@ -506,7 +433,7 @@ __global__ __launch_bounds__(32 * kTabSlices) void attn_bwd_table_kernel(BwdPara
     if (ax) r -= rows_h;
     const int c4 = threadIdx.x, slice = threadIdx.y, HD = p.HD, C = p.nH * HD;
     const bool live = 4 * c4 < HD;
-    const Group gr = decode_group(p, grp);
+    const Window gr = decode_window(p, grp);
     const int win = ax ? p.win_w : p.win_h;
     const int off = r - (win - 1);         // query position minus key position
     const float *A = (ax ? p.aw : p.ah) + grp * p.Tp * win;
@@ -584,30 +511,10 @@ int launch_bwd_hd(const BwdParams &p, long long blocks, size_t lds_bytes, hipStr
     }
 }
 
-// the checks that sgv3d_vit_attention makes of its descriptor, under the caller's name
-int check_desc(const char *who, const sgv3d_vit_attn_desc *desc) {
-    if (!desc) return fail(SGV3D_EINVAL, "%s: null descriptor", who);
-    const sgv3d_vit_attn_desc &d = *desc;
-    if (!(d.batch > 0 && d.height > 0 && d.width > 0 && d.heads > 0 && d.head_dim > 0 && d.win_h > 0 && d.win_w > 0))
-        return fail(SGV3D_EINVAL, "%s: zero or negative dimension (batch %d, map %d x %d, heads %d, head_dim %d, window %d x %d)", who,
-                    d.batch, d.height, d.width, d.heads, d.head_dim, d.win_h, d.win_w);
-    if (!(d.head_dim == 32 || d.head_dim == 64 || d.head_dim == 80))
-        return fail(SGV3D_EINVAL, "%s: head_dim %d is not one of 32, 64, 80", who, d.head_dim);
-    if (!(d.win_h <= 128 && d.win_w <= 128)) return fail(SGV3D_EINVAL, "%s: window %d x %d exceeds 128", who, d.win_h, d.win_w);
-    if (!(3LL * d.heads * d.head_dim < (1LL << 24))) return fail(SGV3D_EINVAL, "%s: heads * head_dim too large", who);
-    return SGV3D_OK;
-}
-
 // ------------------------------------------------------------------------------------------------
 // LayerNorm backward
 // ------------------------------------------------------------------------------------------------
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// One wave per row: mean and rstd as the forward forms them, the two row sums of the gradient in f64, dx; the row's mean and rstd
+// One wave per row: the forward's mean and rstd (ln_row_stats), the two row sums of the gradient in f64, dx; the row's mean and rstd
 // go to the workspace for the weight / bias partials.
 __global__ __launch_bounds__(kBlock) void layernorm_bwd_dx_kernel(long long rows, int c4, const f32x4 *__restrict__ x,
                                                                   const f32x4 *__restrict__ weight, float eps, const f32x4 *dy, f32x4 *dx,
@@ -618,26 +525,14 @@ __global__ __launch_bounds__(kBlock) void layernorm_bwd_dx_kernel(long long rows
     const f32x4 *xr = x + row * c4, *gr = dy + row * c4;
     f32x4 *dr = dx + row * c4;
     const double inv_c = 1.0 / (4.0 * (double)c4);
-    double s = 0.0;
-    for (int i = lane; i < c4; i += 64) {
-        const f32x4 v = xr[i];
-        s += ((double)v[0] + (double)v[1]) + ((double)v[2] + (double)v[3]);
-    }
-    const double mean = wave_sum(s) * inv_c;
-    double sq = 0.0;
-    for (int i = lane; i < c4; i += 64) {
-        const f32x4 v = xr[i];
-        const double e0 = (double)v[0] - mean, e1 = (double)v[1] - mean, e2 = (double)v[2] - mean, e3 = (double)v[3] - mean;
-        sq += (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
-    }
-    const float rstd = (float)(1.0 / sqrt(wave_sum(sq) * inv_c + (double)eps));
+    const LnStats st = ln_row_stats(xr, c4, lane, eps);
     double s1 = 0.0, s2 = 0.0;
     for (int i = lane; i < c4; i += 64) {
         const f32x4 v = xr[i], w = weight[i], d = gr[i];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const double gk = (double)d[k] * (double)w[k];
-            const float xh = (float)((double)v[k] - mean) * rstd;
+            const float xh = ln_xhat(v[k], st);
             s1 += gk;
             s2 += gk * (double)xh;
         }
@@ -648,14 +543,14 @@ __global__ __launch_bounds__(kBlock) void layernorm_bwd_dx_kernel(long long rows
         f32x4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float xh = (float)((double)v[k] - mean) * rstd;
-            o[k] = (float)((double)rstd * ((double)d[k] * (double)w[k] - m1 - (double)xh * m2));
+            const float xh = ln_xhat(v[k], st);
+            o[k] = (float)((double)st.rstd * ((double)d[k] * (double)w[k] - m1 - (double)xh * m2));
         }
         dr[i] = o;
     }
     if (lane == 0) {
-        stats[2 * row] = mean;
-        stats[2 * row + 1] = (double)rstd;
+        stats[2 * row] = st.mean;
+        stats[2 * row + 1] = (double)st.rstd;
     }
 }
 
@@ -668,9 +563,7 @@ __global__ __launch_bounds__(kBlock) void layernorm_bwd_partial_kernel(long long
     const long long r0 = (long long)blockIdx.x * kLnChunk, r1 = r0 + kLnChunk < rows ? r0 + kLnChunk : rows;
     double sw = 0.0, sb = 0.0;
     for (long long r = r0; r < r1; ++r) {
-        const double mean = stats[2 * r];
-        const float rstd = (float)stats[2 * r + 1];
-        const float xh = (float)((double)x[r * C + c] - mean) * rstd;
+        const float xh = ln_xhat(x[r * C + c], LnStats{stats[2 * r], (float)stats[2 * r + 1]});
         const double d = (double)dy[r * C + c];
         sw += d * (double)xh;
         sb += d;
@@ -693,11 +586,10 @@ __global__ __launch_bounds__(kBlock) void layernorm_bwd_finish_kernel(int chunks
 }
 
 // ------------------------------------------------------------------------------------------------
-// GELU backward: dx = dy (Phi(x) + x phi(x)); Phi as the forward writes it (erfc in the left tail)
+// GELU backward: dx = dy (Phi(x) + x phi(x)); Phi from the forward's erf term (gelu_erf_term)
 // ------------------------------------------------------------------------------------------------
 __device__ inline float gelu_grad1(float x, float dy) {
-    const float z = x * 0.70710678118654752440f;
-    const float cdf = 0.5f * (x < 0.f ? erfcf(-z) : 1.0f + erff(z));
+    const float cdf = 0.5f * gelu_erf_term(x);
     const float pdf = 0.39894228040143267794f * expf(-0.5f * x * x);
     return dy * fmaf(x, pdf, cdf);
 }
@@ -774,7 +666,7 @@ extern "C" int sgv3d_vit_attention_lse(const sgv3d_vit_attn_desc *desc, const fl
 }
 
 extern "C" size_t sgv3d_vit_attention_backward_workspace_bytes(const sgv3d_vit_attn_desc *desc) {
-    if (check_desc("vit_attention_backward_workspace_bytes", desc) != SGV3D_OK) return 0;
+    if (check_attn_desc("vit_attention_backward_workspace_bytes", desc, 0) != SGV3D_OK) return 0;
     return sizeof(float) * (size_t)bwd_layout(*desc, true).total;     // with tables: an upper bound for the call without
 }
 
@@ -782,7 +674,7 @@ extern "C" int sgv3d_vit_attention_backward(const sgv3d_vit_attn_desc *desc, con
                                             const float *rel_pos_h, const float *rel_pos_w, const float *out, const float *lse,
                                             const float *dout, float *dqkv, float *dpad_qkv, float *drel_pos_h, float *drel_pos_w,
                                             void *workspace, size_t workspace_bytes, void *stream) {
-    const int rc = check_desc("vit_attention_backward", desc);
+    const int rc = check_attn_desc("vit_attention_backward", desc, 0);
     if (rc != SGV3D_OK) return rc;
     const sgv3d_vit_attn_desc &d = *desc;
     SGV3D_REQUIRE((rel_pos_h == nullptr) == (rel_pos_w == nullptr),
@@ -799,7 +691,7 @@ extern "C" int sgv3d_vit_attention_backward(const sgv3d_vit_attn_desc *desc, con
     const BwdLayout L = bwd_layout(d, rel);
     SGV3D_REQUIRE(L.G * L.Tp < (1LL << 31) && L.G * (2LL * d.win_h + 2LL * d.win_w) < (1LL << 31),
                   "vit_attention_backward: too many workgroups");
-    const int ah_ld = rel ? (d.win_h | 1) : 0, aw_ld = rel ? (d.win_w | 1) : 0;
+    const int ah_ld = odd_ld(rel, d.win_h), aw_ld = odd_ld(rel, d.win_w);
     const size_t tile_floats = d.head_dim == 32 ? BwdGeom<32>::floats : d.head_dim == 64 ? BwdGeom<64>::floats : BwdGeom<80>::floats;
     const size_t lds_keys = sizeof(float) * tile_floats, lds_q = lds_keys + sizeof(float) * (size_t)kTile * (ah_ld + aw_ld);
     // lds_q is at most 2 * 64 * 88 + 64 * (129 + 129) floats = 111 104 bytes of the 160 KB: the window is at most 128 x 128
@@ -808,11 +700,9 @@ extern "C" int sgv3d_vit_attention_backward(const sgv3d_vit_attn_desc *desc, con
                     sizeof(float) * (size_t)L.total);
 
     BwdParams p;
-    p.B = d.batch, p.H = d.height, p.W = d.width, p.nH = d.heads, p.HD = d.head_dim, p.win_h = d.win_h, p.win_w = d.win_w;
-    p.nwy = cdiv(d.height, d.win_h), p.nwx = cdiv(d.width, d.win_w);
-    p.T = (int)L.T, p.Tp = (int)L.Tp, p.nt = (int)L.nt, p.ah_ld = ah_ld, p.aw_ld = aw_ld;
-    p.scale = 1.0f / sqrtf((float)d.head_dim);
-    p.inv_win_w = 1.0f / (float)d.win_w;
+    fill_window(p, d);
+    p.HD = d.head_dim, p.Tp = (int)L.Tp, p.nt = (int)L.nt, p.ah_ld = ah_ld, p.aw_ld = aw_ld;
+    p.scale = softmax_scale(d.head_dim);
     p.qkv = qkv, p.pad = pad_qkv, p.rh = rel_pos_h, p.rw = rel_pos_w, p.out = out, p.lse = lse, p.dout = dout;
     p.dqkv = dqkv, p.dpad = dpad_qkv, p.drh = drel_pos_h, p.drw = drel_pos_w;
     float *ws = static_cast<float *>(workspace);

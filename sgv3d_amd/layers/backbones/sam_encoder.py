@@ -37,13 +37,9 @@ def vit_attention(qkv, num_heads, window, pad_qkv=None, rel_pos_h=None, rel_pos_
     assert qkv.is_contiguous() and qkv.dtype == torch.float32 and qkv.dim() == 4 and qkv.shape[-1] % (3 * num_heads) == 0
     b, h, w, c3 = (int(s) for s in qkv.shape)
     c = c3 // 3
-    d = _lib.VitAttnDesc(b, h, w, int(num_heads), c // int(num_heads), int(window[0]), int(window[1]))
-    for name, tab, win in (("rel_pos_h", rel_pos_h, d.win_h), ("rel_pos_w", rel_pos_w, d.win_w)):
-        if tab is not None and tuple(tab.shape) != (2 * win - 1, d.head_dim):
-            raise _lib.SGV3DError(f"{name} has shape {tuple(tab.shape)}, the window needs {(2 * win - 1, d.head_dim)}: "
-                                  "interpolated relative-position tables are not built")
+    d = _lib.vit_attn_desc(qkv, num_heads, window, pad_qkv, rel_pos_h, rel_pos_w)
     if pad_qkv is not None:
-        assert pad_qkv.numel() == c3 and pad_qkv.is_contiguous()
+        assert pad_qkv.is_contiguous()
     if out is None:
         out = torch.empty(b, h, w, c, dtype=torch.float32, device=qkv.device)
     lib = _lib.load()
@@ -60,15 +56,9 @@ def vit_attention_bf16(qkv, num_heads, window, pad_qkv=None, rel_pos_h=None, rel
     assert qkv.is_contiguous() and qkv.dtype == torch.bfloat16 and qkv.dim() == 4 and qkv.shape[-1] % (3 * num_heads) == 0
     b, h, w, c3 = (int(s) for s in qkv.shape)
     c = c3 // 3
-    d = _lib.VitAttnDesc(b, h, w, int(num_heads), c // int(num_heads), int(window[0]), int(window[1]))
-    for name, tab, win in (("rel_pos_h", rel_pos_h, d.win_h), ("rel_pos_w", rel_pos_w, d.win_w)):
-        if tab is not None and tuple(tab.shape) != (2 * win - 1, d.head_dim):
-            raise _lib.SGV3DError(f"{name} has shape {tuple(tab.shape)}, the window needs {(2 * win - 1, d.head_dim)}: "
-                                  "interpolated relative-position tables are not built")
+    d = _lib.vit_attn_desc(qkv, num_heads, window, pad_qkv, rel_pos_h, rel_pos_w)
     for t in (pad_qkv, rel_pos_h, rel_pos_w):
         assert t is None or (t.dtype == torch.float32 and t.is_contiguous())
-    if pad_qkv is not None:
-        assert pad_qkv.numel() == c3
     if out is None:
         out = torch.empty(b, h, w, c, dtype=torch.bfloat16, device=qkv.device)
     assert out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (b, h, w, c)
@@ -302,7 +292,7 @@ class Attention(nn.Module):
             for name, tab, win in (("rel_pos_h", self.rel_pos_h, window[0]), ("rel_pos_w", self.rel_pos_w, window[1])):
                 if tab.shape[0] != 2 * win - 1:
                     raise _lib.SGV3DError(f"Attention: {name} has {tab.shape[0]} rows, a {window[0]} x {window[1]} window needs "
-                                          f"{2 * win - 1}: interpolated relative-position tables are not built")
+                                          f"{2 * win - 1}: {_lib.REL_POS_NOT_BUILT}")
         require_device(x, "Attention", bf16_ok=True)
         with torch.no_grad():
             qkv = self._pqkv.get(self.qkv.weight, self.qkv.bias)(x, out_dtype=x.dtype)

@@ -21,24 +21,11 @@ def _f32(*tensors):
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), "contiguous float32 tensors on the GPU are expected"
 
 
-def _desc(qkv, num_heads, window, pad_qkv, rel_pos_h, rel_pos_w):
-    assert qkv.dim() == 4 and qkv.shape[-1] % (3 * num_heads) == 0
-    b, h, w, c3 = (int(s) for s in qkv.shape)
-    d = _lib.VitAttnDesc(b, h, w, int(num_heads), c3 // 3 // int(num_heads), int(window[0]), int(window[1]))
-    for name, tab, win in (("rel_pos_h", rel_pos_h, d.win_h), ("rel_pos_w", rel_pos_w, d.win_w)):
-        if tab is not None and tuple(tab.shape) != (2 * win - 1, d.head_dim):
-            raise _lib.SGV3DError(f"{name} has shape {tuple(tab.shape)}, the window needs {(2 * win - 1, d.head_dim)}: "
-                                  "interpolated relative-position tables are not built")
-    if pad_qkv is not None:
-        assert pad_qkv.numel() == c3
-    return d
-
-
 # ---- thin calls ----
 def attention_lse(qkv, num_heads, window, pad_qkv=None, rel_pos_h=None, rel_pos_w=None):
     """sgv3d_vit_attention_lse: -> out [B, H, W, C] (the bits of sgv3d_vit_attention), lse [B, heads, H, W]."""
     _f32(qkv, pad_qkv, rel_pos_h, rel_pos_w)
-    d = _desc(qkv, num_heads, window, pad_qkv, rel_pos_h, rel_pos_w)
+    d = _lib.vit_attn_desc(qkv, num_heads, window, pad_qkv, rel_pos_h, rel_pos_w)
     out = torch.empty(d.batch, d.height, d.width, d.heads * d.head_dim, dtype=torch.float32, device=qkv.device)
     lse = torch.empty(d.batch, d.heads, d.height, d.width, dtype=torch.float32, device=qkv.device)
     with torch.cuda.device(qkv.device):
@@ -51,7 +38,7 @@ def attention_lse(qkv, num_heads, window, pad_qkv=None, rel_pos_h=None, rel_pos_
 def attention_backward(qkv, num_heads, window, pad_qkv, rel_pos_h, rel_pos_w, out, lse, dout):
     """sgv3d_vit_attention_backward: -> dqkv, dpad_qkv (None without pad_qkv), drel_pos_h, drel_pos_w (None without tables)."""
     _f32(qkv, pad_qkv, rel_pos_h, rel_pos_w, out, lse, dout)
-    d = _desc(qkv, num_heads, window, pad_qkv, rel_pos_h, rel_pos_w)
+    d = _lib.vit_attn_desc(qkv, num_heads, window, pad_qkv, rel_pos_h, rel_pos_w)
     assert out.shape == dout.shape == (d.batch, d.height, d.width, d.heads * d.head_dim) and lse.shape == (d.batch, d.heads, d.height, d.width)
     dev = qkv.device
     lib = _lib.load()

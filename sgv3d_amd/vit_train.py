@@ -91,7 +91,7 @@ def attention_forward(attn, x, window=None, residual=None):
         for name, tab, win in (("rel_pos_h", rel[0], window[0]), ("rel_pos_w", rel[1], window[1])):
             if tab.shape[0] != 2 * win - 1:
                 raise _lib.SGV3DError(f"Attention: {name} has {tab.shape[0]} rows, a {window[0]} x {window[1]} window needs "
-                                      f"{2 * win - 1}: interpolated relative-position tables are not built")
+                                      f"{2 * win - 1}: {_lib.REL_POS_NOT_BUILT}")
     qkv = _packed(attn._pqkv, x.contiguous(), attn.qkv.weight, attn.qkv.bias)
     a = vit_grad.attention(qkv, attn.num_heads, window, attn.qkv.bias, *rel)
     return _packed(attn._pproj, a, attn.proj.weight, attn.proj.bias, residual)
