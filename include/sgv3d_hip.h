@@ -379,10 +379,31 @@ int sgv3d_conv2d_x3_shortcut_forward(const sgv3d_conv_desc *desc_a, const float 
  * unknown variant, a short pack and weights / scale / shift / output that are not 16-B aligned. */
 int sgv3d_stem_pool_x3_forward(int batch, int h, int w, const float *x_nchw, const void *w_x3, size_t w_bytes, const float *scale,
                                const float *shift, float *y_nhwc, int y_ld, int variant, void *stream);
+/* The F(4x4) tile lattice of ONE axis of n pixels at dilation dil, on the host (no GPU call): a dilated layer either gives every
+ * phase p = 0 .. dil - 1 (pixels p, p + dil, ...) its own tiles, dil * ceil(ceil(n / dil) / 4), or stacks the phases on one line
+ * with a single zero element between neighbours and cuts that, ceil((n + dil - 1) / 4) -- whichever is fewer (the first on a
+ * tie; dil 1: the plain ceil(n / 4)).  *tiles, *stacked (any may be null): that choice.  pixels (may be null): the pixel
+ * coordinate of the `count` (1..6) elements from 4 * tile + k0 on (k0 -1: a tile's six inputs, 0: its four outputs), -1 for a
+ * separator or a position outside the axis.  sgv3d_conv2d_winograd4_forward uses tiles(out_h) * tiles(out_w) tiles per image. */
+int sgv3d_wino4_lattice_axis(int n, int dil, int tile, int k0, int count, int *tiles, int *stacked, int *pixels);
 size_t sgv3d_conv2d_winograd4_workspace_bytes(const sgv3d_conv_desc *desc /*host*/);
 int sgv3d_conv2d_winograd4_forward(const sgv3d_conv_desc *desc /*host*/, const float *x, const float *u_packed,
                                    const float *scale, const float *bias, const float *residual, float *y,
                                    void *workspace, size_t workspace_bytes, void *stream);
+
+/* n = 1..4 F(4x4) layers that read the SAME input (ASPP's dilated branches): descs[0..n) contiguous, each as for
+ * sgv3d_conv2d_winograd4_forward with desc.tile = SGV3D_TILE_X3 | variant (NHWC output, no residual, no split-K; the layers may
+ * differ in dilation, weights, folded BN, output pointer / slice and variant; batch, map, cin, x_ld, x_coff must agree).  One
+ * launch of the input transform for all layers, the n grouped GEMMs as the single entry point launches them, one launch of the
+ * output transform; per element the arithmetic of n single calls, so the result equals theirs bit for bit.  u_packed / scale /
+ * bias / y: host arrays of n device pointers (a scale or bias may be null).  Workspace: the layers' own workspaces one after
+ * another (sgv3d_conv2d_winograd4_multi_workspace_bytes; 0 for n outside 1..4 or a bad descriptor).  Refuses (SGV3D_EINVAL) n
+ * outside 1..4, null pointers, layers on different inputs or geometry, tiles other than f32x3 ones, misaligned pointers, a layer
+ * whose M needs more than one channel pass; SGV3D_ENOSPACE for a short workspace. */
+size_t sgv3d_conv2d_winograd4_multi_workspace_bytes(int n, const sgv3d_conv_desc *descs /*host*/);
+int sgv3d_conv2d_winograd4_forward_multi(int n, const sgv3d_conv_desc *descs /*host*/, const float *x, const void *const *u_packed,
+                                         const float *const *scale, const float *const *bias, float *const *y, void *workspace,
+                                         size_t workspace_bytes, void *stream);
 
 /* Packed weight geometry for a GEMM with `k` reduction elements and `n` output columns. */
 void sgv3d_conv_pack_geometry(int k, int n, int *k_pad, int *n_pad);

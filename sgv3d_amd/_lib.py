@@ -117,8 +117,11 @@ _PROTOS = {
     "sgv3d_conv2d_x3_forward": (c_int, [c_void_p] * 8 + [c_size_t, c_void_p]),
     "sgv3d_conv2d_x3_shortcut_forward": (c_int, [c_void_p] * 12),
     "sgv3d_stem_pool_x3_forward": (c_int, [c_int] * 3 + [c_void_p, c_void_p, c_size_t] + [c_void_p] * 3 + [c_int, c_int, c_void_p]),
+    "sgv3d_wino4_lattice_axis": (c_int, [c_int] * 5 + [c_void_p] * 3),
     "sgv3d_conv2d_winograd4_workspace_bytes": (c_size_t, [ctypes.POINTER(ConvDesc)]),
     "sgv3d_conv2d_winograd4_forward": (c_int, [ctypes.POINTER(ConvDesc)] + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    "sgv3d_conv2d_winograd4_multi_workspace_bytes": (c_size_t, [c_int, c_void_p]),
+    "sgv3d_conv2d_winograd4_forward_multi": (c_int, [c_int] + [c_void_p] * 7 + [c_size_t, c_void_p]),
     "sgv3d_maxpool3x3s2": (c_int, [c_int] * 4 + [c_void_p] * 3),
     "sgv3d_maxpool3x3s2_bf16": (c_int, [c_int] * 4 + [c_void_p] * 3),
     "sgv3d_nchw_to_nhwc": (c_int, [c_int] * 5 + [c_void_p] * 3),

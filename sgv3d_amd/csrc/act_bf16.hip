@@ -8,6 +8,7 @@
 //   deform_im2col3x3   mmcv DeformConv2dPack sampling             lss_fpn.py:190-198
 // All HBM-bound: algorithmic bytes = the tensors read + written once.
 #include "common.hpp"
+#include "avgpool.hpp"
 
 using namespace sgv3d;
 
@@ -18,7 +19,6 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBlock = 256;
-constexpr int kAvgChunks = 32;
 
 struct F8 {
     float v[8];
@@ -51,33 +51,15 @@ __global__ __launch_bounds__(kBlock) void scale_channels_bf16_kernel(long long t
     st8(y + i * 8, v);
 }
 
-// same two deterministic stages as the f32 kernel: partial sums over pixel ranges (f32), then a fixed-order final sum
-__global__ __launch_bounds__(kBlock) void global_avgpool_bf16_partial_kernel(int P, int C, int ld, const __bf16 *__restrict__ x,
-                                                                             float *__restrict__ part) {
-    __shared__ float red[4][64];
-    const int b = blockIdx.z, chunk = blockIdx.y;
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int g = threadIdx.x >> 6;
-    const int per = (P + kAvgChunks - 1) / kAvgChunks;
-    const int p0 = chunk * per, p1 = min(P, p0 + per);
-    float s = 0.f;
-    if (c < C)
-        for (int p = p0 + g; p < p1; p += 4) s += (float)x[((long long)b * P + p) * ld + c];
-    red[g][threadIdx.x & 63] = s;
-    __syncthreads();
-    if (g == 0 && c < C)
-        part[((long long)b * kAvgChunks + chunk) * C + c] =
-            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+// the two deterministic stages of avgpool.hpp, as the f32 kernels run them (misc_layers.hip): the same bits on the same values
+__global__ __launch_bounds__(kAvgBlock) void global_avgpool_bf16_partial_kernel(int P, int C, int ld, const __bf16 *__restrict__ x,
+                                                                                float *__restrict__ part) {
+    avgpool_partial_scalar(P, C, ld, x, part);
 }
 
-__global__ __launch_bounds__(kBlock) void global_avgpool_bf16_final_kernel(int B, int P, int C, const float *__restrict__ part,
-                                                                           float *__restrict__ y) {
-    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= (long long)B * C) return;
-    const int b = (int)(i / C), c = (int)(i - (long long)b * C);
-    float s = 0.f;
-    for (int k = 0; k < kAvgChunks; ++k) s += part[((long long)b * kAvgChunks + k) * C + c];
-    y[i] = s / (float)P;
+__global__ __launch_bounds__(kAvgBlock) void global_avgpool_bf16_final_kernel(int P, int C, const float *__restrict__ part,
+                                                                              float *__restrict__ y) {
+    avgpool_final(P, C, part, y);
 }
 
 __global__ __launch_bounds__(kBlock) void broadcast_channels_bf16_kernel(long long total8, int P, int C8, int ld, int coff,
@@ -195,10 +177,10 @@ extern "C" int sgv3d_global_avgpool_bf16(int batch, int pixels, int channels, in
     if (workspace_bytes < sizeof(float) * (size_t)batch * kAvgChunks * channels)
         return fail(SGV3D_ENOSPACE, "global_avgpool_bf16: workspace too small (sgv3d_global_avgpool_workspace_bytes)");
     float *part = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(global_avgpool_bf16_partial_kernel, dim3(cdiv(channels, 64), kAvgChunks, batch), dim3(kBlock), 0,
+    hipLaunchKernelGGL(global_avgpool_bf16_partial_kernel, dim3(cdiv(channels, 64), kAvgChunks, batch), dim3(kAvgBlock), 0,
                        as_stream(stream), pixels, channels, x_ld, static_cast<const __bf16 *>(x), part);
-    hipLaunchKernelGGL(global_avgpool_bf16_final_kernel, dim3(cdiv((long long)batch * channels, kBlock)), dim3(kBlock), 0,
-                       as_stream(stream), batch, pixels, channels, part, y);
+    hipLaunchKernelGGL(global_avgpool_bf16_final_kernel, dim3(cdiv(channels, 32), batch), dim3(kAvgBlock), 0, as_stream(stream), pixels,
+                       channels, part, y);
     return check_launch("global_avgpool_bf16_kernel");
 }
 

@@ -1,6 +1,7 @@
 // Small layers around the convolutions (all NHWC fp32, all HBM/latency-bound, no MFMA).
 // Reference call sites are cited per kernel; paths relative to the reference repo.
 #include "common.hpp"
+#include "avgpool.hpp"
 
 using namespace sgv3d;
 
@@ -106,39 +107,47 @@ __global__ __launch_bounds__(kBlock) void nhwc_to_nchw_kernel(int C, long long H
     }
 }
 
-// nn.AdaptiveAvgPool2d((1,1))  (ASPP.global_avg_pool, layers/backbones/lss_fpn.py:81-86)
-// Two deterministic stages: kAvgChunks workgroups per (image, 64-channel group) sum a pixel range each
-// into the caller's workspace, then one wave per output adds the partials in fixed order.
-constexpr int kAvgChunks = 32;
-
-__global__ __launch_bounds__(kBlock) void global_avgpool_partial_kernel(int P, int C, int ld,
-                                                                        const float *__restrict__ x,
-                                                                        float *__restrict__ part) {
-    __shared__ float red[4][64];
+// nn.AdaptiveAvgPool2d((1,1))  (ASPP.global_avg_pool, layers/backbones/lss_fpn.py:81-86): the two deterministic stages of
+// avgpool.hpp.  Stage 1 with 16-byte loads where the channels allow it: one thread = one channel quad x one pixel lane,
+// 64 quads x 4 lanes per workgroup, grid (ceil(C / 256), kAvgChunks, batch); per channel the sums are those of the scalar form.
+__global__ __launch_bounds__(kAvgBlock) void global_avgpool_partial_kernel(int P, int C, int ld,
+                                                                           const float *__restrict__ x,
+                                                                           float *__restrict__ part) {
+    __shared__ float4 red[4][64];
     const int b = blockIdx.z, chunk = blockIdx.y;
-    const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int g = threadIdx.x >> 6;
-    const int per = (P + kAvgChunks - 1) / kAvgChunks;
-    const int p0 = chunk * per, p1 = min(P, p0 + per);
-    float s = 0.f;
-    if (c < C)
-        for (int p = p0 + g; p < p1; p += 4) s += x[((long long)b * P + p) * ld + c];
-    red[g][threadIdx.x & 63] = s;
+    const int q = threadIdx.x & 63, g = threadIdx.x >> 6;
+    const int c = (blockIdx.x * 64 + q) * 4;
+    int p0, p1;
+    avgpool_chunk(P, chunk, p0, p1);
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (c < C) {
+        const float *xb = x + ((long long)b * P) * ld + c;
+#pragma unroll 4
+        for (int p = p0 + g; p < p1; p += 4) {
+            const float4 v = *reinterpret_cast<const float4 *>(xb + (long long)p * ld);
+            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        }
+    }
+    red[g][q] = s;
     __syncthreads();
-    if (g == 0 && c < C)
-        part[((long long)b * kAvgChunks + chunk) * C + c] =
-            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    if (g == 0 && c < C) {
+        const float4 r0 = red[0][q], r1 = red[1][q], r2 = red[2][q], r3 = red[3][q];
+        *reinterpret_cast<float4 *>(part + ((long long)b * kAvgChunks + chunk) * C + c) =
+            make_float4((r0.x + r1.x) + (r2.x + r3.x), (r0.y + r1.y) + (r2.y + r3.y), (r0.z + r1.z) + (r2.z + r3.z),
+                        (r0.w + r1.w) + (r2.w + r3.w));
+    }
 }
 
-__global__ __launch_bounds__(kBlock) void global_avgpool_final_kernel(int B, int P, int C,
-                                                                      const float *__restrict__ part,
-                                                                      float *__restrict__ y) {
-    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;   // b*C + c
-    if (i >= (long long)B * C) return;
-    const int b = (int)(i / C), c = (int)(i - (long long)b * C);
-    float s = 0.f;
-    for (int k = 0; k < kAvgChunks; ++k) s += part[((long long)b * kAvgChunks + k) * C + c];
-    y[i] = s / (float)P;
+// ... one channel per thread: C or the leading dimension no multiple of 4, or a base that is not 16-B aligned
+__global__ __launch_bounds__(kAvgBlock) void global_avgpool_partial_scalar_kernel(int P, int C, int ld,
+                                                                                  const float *__restrict__ x,
+                                                                                  float *__restrict__ part) {
+    avgpool_partial_scalar(P, C, ld, x, part);
+}
+
+__global__ __launch_bounds__(kAvgBlock) void global_avgpool_final_kernel(int P, int C, const float *__restrict__ part,
+                                                                         float *__restrict__ y) {
+    avgpool_final(P, C, part, y);
 }
 
 // y[b,n] = act(scale[n] * dot(W[n,:], x[b,:]) + bias[n]) : one wave per output
@@ -514,10 +523,15 @@ extern "C" int sgv3d_global_avgpool(int batch, int pixels, int channels, int x_l
     if (workspace_bytes < sgv3d_global_avgpool_workspace_bytes(batch, channels))
         return fail(SGV3D_ENOSPACE, "global_avgpool: workspace too small");
     float *part = static_cast<float *>(workspace);
-    hipLaunchKernelGGL(global_avgpool_partial_kernel, dim3(cdiv(channels, 64), kAvgChunks, batch), dim3(kBlock), 0,
-                       as_stream(stream), pixels, channels, x_ld, x, part);
-    hipLaunchKernelGGL(global_avgpool_final_kernel, dim3(cdiv((long long)batch * channels, kBlock)), dim3(kBlock), 0,
-                       as_stream(stream), batch, pixels, channels, part, y);
+    const bool quads = channels % 4 == 0 && x_ld % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(part)) & 15) == 0;
+    if (quads)
+        hipLaunchKernelGGL(global_avgpool_partial_kernel, dim3(cdiv(channels, 256), kAvgChunks, batch), dim3(kAvgBlock), 0,
+                           as_stream(stream), pixels, channels, x_ld, x, part);
+    else
+        hipLaunchKernelGGL(global_avgpool_partial_scalar_kernel, dim3(cdiv(channels, 64), kAvgChunks, batch), dim3(kAvgBlock), 0,
+                           as_stream(stream), pixels, channels, x_ld, x, part);
+    hipLaunchKernelGGL(global_avgpool_final_kernel, dim3(cdiv(channels, 32), batch), dim3(kAvgBlock), 0, as_stream(stream), pixels,
+                       channels, part, y);
     return check_launch("global_avgpool_kernel");
 }
 

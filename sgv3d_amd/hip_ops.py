@@ -221,6 +221,29 @@ WINO4_X3_TILES = conv_tiles.family("wino4_x3")
 X3_TILE_ROWS = {t: TILES[t].bm for t in WINO4_X3_TILES}
 X3_TILE_COLS = {t: TILES[t].bn for t in WINO4_X3_TILES}
 WINO4_TILES = conv_tiles.family("wino4", "wino4_x3")
+
+
+def wino4_axis_tiles(n, dil):
+    """F(4x4) tiles along one axis of ``n`` pixels at dilation ``dil`` (csrc/conv_wino4.hip: wino4_axis): every phase its own tiles,
+    or the phases stacked on one line with a zero element between neighbours -- whichever is fewer."""
+    dil = max(1, int(dil))
+    return min(dil * -(-(-(-n // dil)) // 4), -(-(n + dil - 1) // 4))
+
+
+def wino4_tiles(batch, oh, ow, dil):
+    """Rows per position of the three-launch F(4x4) path before padding to the GEMM's m-tile."""
+    return batch * wino4_axis_tiles(oh, dil) * wino4_axis_tiles(ow, dil)
+
+
+def _wino4_tiles_per_phase(batch, oh, ow, dil):
+    """The tile count with every sub-grid phase on tiles of its own (what a dilated layer ran before the lattice; dil 1: the same
+    number).  The candidate list of the f32x3 position GEMM and the profile's executed flops are part of the recorded dispatch
+    (tests/golden/conv_dispatch.json.gz) and keep counting this way: for the three dilated ASPP layers the list is the one their
+    committed choices were measured against, and the profile reports up to a quarter more MFMA work than the launch executes."""
+    dil = max(1, int(dil))
+    return batch * dil * dil * -(-(-(-oh // dil)) // 4) * -(-(-(-ow // dil)) // 4)
+
+
 WINO4_G48 = _os.environ.get("SGV3D_WINO4_G48", "1") != "0"     # 0: never a candidate
 # 0: the f32x3 position GEMM is never a candidate -- every product of the f32 path on the f32 MFMA (bench.py's native_f32_value)
 WINO4_X3 = _os.environ.get("SGV3D_WINO4_X3", "1") != "0"
@@ -790,8 +813,7 @@ class PackedConv:
             if T.flops == "wino4":
                 # the grouped GEMM of the three-launch F(4x4) path: 36 positions x rows (tiles padded to the GEMM's m-tile)
                 oh, ow = self.out_hw(H, W)
-                dil = max(1, self.dil)
-                tiles = B * dil * dil * -(-(-(-oh // dil)) // 4) * -(-(-(-ow // dil)) // 4)
+                tiles = _wino4_tiles_per_phase(B, oh, ow, self.dil)
                 mfma = 2.0 * 36 * (-(-tiles // T.bm) * T.bm) * self.cin * self.cout
             elif T.flops == "direct_k32":
                 mfma = 2.0 * gemm_m * self.cout * _up32(self.cin * self.kh * self.kw)
@@ -1003,8 +1025,7 @@ class PackedConv:
     def _x3_tiles(self, d):
         """The shapes of the f32x3 position GEMM worth timing for this layer: m-tiles that waste at most 10 % of the rows as padding
         (the smallest waste always), 160 columns only where they cover cout with fewer idle columns than 128 do."""
-        dil = max(1, int(d.dil))
-        tiles = d.batch * dil * dil * -(-(-(-d.out_h // dil)) // 4) * -(-(-(-d.out_w // dil)) // 4)
+        tiles = _wino4_tiles_per_phase(d.batch, d.out_h, d.out_w, d.dil)
         waste = {r: (-(-tiles // r) * r - tiles) / tiles for r in sorted(set(X3_TILE_ROWS.values()))}
         best = min(waste.values())
         ms = [r for r in waste if waste[r] <= max(best, 0.10) and (r <= 64 or tiles >= r)]
@@ -1155,7 +1176,7 @@ def switch_state():
     g = globals()
     return tuple(g.get(k) for k in ("AUTOTUNE", "SPLIT_K", "WINOGRAD", "FUSED_HEAD", "HEAD_PATH", "MFMA_BF16", "BF16_ACTIVATIONS",
                                     "MFMA_F32X3", "MFIRST", "WINO4", "WINO_HALF", "PATCH_BF16", "DW_BF16", "DW_DEEP", "DW_NARROW",
-                                    "DW_SPLIT_K", "DW_DEEP_MAX_WGS", "PAIR_BF16", "TUNE_STREAMS", "PARALLEL_BRANCHES", "F4RES", "OCC5", "WINO4_G48", "DCN_FUSED", "WINO4_X3", "PW_X3",
+                                    "DW_SPLIT_K", "DW_DEEP_MAX_WGS", "PAIR_BF16", "TUNE_STREAMS", "PARALLEL_BRANCHES", "F4RES", "OCC5", "WINO4_G48", "DCN_FUSED", "WINO4_X3", "WINO4_MULTI", "PW_X3",
                                     "DCN_FUSED_BF16", "DCN_FUSED_TRAIN", "TRAIN_BF16_STORAGE", "SHORTCUT_X3", "DECONV_X3", "VIT_BF16", "STEM_FUSED"))
 
 
@@ -1322,6 +1343,112 @@ def conv_shortcut_choice(c3, ds, mid, x):
     on = t1 < t2
     tune_record(sig, [1, best] if on else [0, 0])
     return best if on else 0
+
+# fp32 path: sibling F(4x4) layers on ONE input (ASPP's three dilated branches) with one launch of the input transform and one of
+# the output transform for all of them (csrc/conv_wino4.hip: sgv3d_conv2d_winograd4_forward_multi) instead of one each; the
+# grouped GEMMs run as they do per layer, and the result is bit-equal.  0 (SGV3D_WINO4_MULTI=0): always the per-layer calls.
+WINO4_MULTI = _os.environ.get("SGV3D_WINO4_MULTI", "1") != "0"
+WINO4_MULTI_MAX = 4
+
+
+def _wino4_sibling_choice(conv, x):
+    """(tile, split-K) ``conv(x)`` runs with, as far as it is known without a launch: the layer's own fixed tile, else what its
+    first call on this input shape looked up or measured (``_tile_cache``); (0, 0) before that call and where the fixed rule
+    decides per call."""
+    B, H, W, _ = (int(v) for v in x.shape)
+    t = int(conv.tile)
+    if t in WINO4_X3_TILES:
+        return t, 1
+    return conv._tile_cache.get((B, H, W, t, 0, MFMA_BF16, MFMA_F32X3, CONV_NORMAL, False, False, 0), (0, 0))
+
+
+def wino4_multi_eligible(convs, x, out=None, y_coffs=None, training=False):
+    """``convs`` are 2..4 F(4x4) layers (3x3 / stride 1 / pad == dilation, f32, the same cin) applied to the same f32 NHWC ``x`` in
+    the fp32 mode, outside training and SGV3D_PARALLEL_BRANCHES, writing channel slices of an f32 NHWC ``out``."""
+    if not (WINO4_MULTI and WINO4_X3 and WINO4 and WINOGRAD and not MFMA_BF16 and not MFMA_F32X3 and not PARALLEL_BRANCHES and not training):
+        return False
+    if not 2 <= len(convs) <= WINO4_MULTI_MAX or x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous():
+        return False
+    if int(x.shape[0]) < 1 or int(x.shape[-1]) % 4:
+        return False
+    if any((not c.wino4_ok()) or c.cin != convs[0].cin or c.cin > int(x.shape[-1]) for c in convs):
+        return False
+    if out is not None:
+        ld = int(out.shape[-1])
+        if (out.dtype != torch.float32 or out.dim() != 4 or not out.is_contiguous() or tuple(out.shape[:3]) != tuple(x.shape[:3]) or ld % 4
+                or y_coffs is None or len(y_coffs) != len(convs)
+                or any(int(o) % 4 or int(o) < 0 or int(o) + c.cout > ld for o, c in zip(y_coffs, convs))):
+            return False
+    return True
+
+
+def wino4_multi_signature(convs, x):
+    B, H, W, _ = (int(v) for v in x.shape)
+    return (f"pair|wino4multi|{'+'.join(f'{c.cout}x{c.cin}d{c.dil}' for c in convs)}|{B}x{H}x{W}|ts{TUNE_STREAMS}")
+
+
+def wino4_multi(convs, x, out, y_coffs, tiles):
+    """``convs[l](x, out, y_coff=y_coffs[l], tile=tiles[l], split_k=1)`` for all l through the multi entry point: one input-transform
+    launch, the grouped GEMMs, one output-transform launch."""
+    n = len(convs)
+    if not wino4_multi_eligible(convs, x, out, y_coffs) or len(tiles) != n or any(int(t) not in WINO4_X3_TILES for t in tiles):
+        raise _lib.SGV3DError("wino4_multi covers 2..4 F(4x4) layers with f32x3 tiles on one f32 NHWC input in the fp32 mode")
+    B, H, W, x_ld = (int(v) for v in x.shape)
+    lib = _lib.load()
+    descs = (ConvDesc * n)()
+    us, flops, nbytes = [], 0.0, 4.0 * B * H * W * convs[0].cin_real
+    for l, (c, t) in enumerate(zip(convs, tiles)):
+        d = descs[l]
+        d.batch, d.in_h, d.in_w, d.cin = B, H, W, c.cin
+        d.out_h, d.out_w, d.cout = H, W, c.cout
+        d.kh, d.kw, d.stride, d.pad, d.dil = 3, 3, 1, c.pad, c.dil
+        d.x_ld, d.x_coff, d.y_ld, d.y_coff = x_ld, 0, int(out.shape[-1]), int(y_coffs[l])
+        d.res_ld, d.relu, d.mode, d.deconv_ks = 0, 1 if c.relu else 0, CONV_NORMAL, c.ks
+        T = TILES[int(t)]
+        us.append(c._form(T.form))
+        d.k_pad, d.cout_pad, d.tile, d.x_nchw, d.k_order, d.split_k = c.cin, c.wino4_x3_cout_pad, T.abi, 0, c.k_order, 1
+        flops += 2.0 * B * H * W * c.cout_real * c.cin_real * 9
+        nbytes += 4.0 * c.cout_real * c.cin_real * 9 + 4.0 * B * H * W * c.cout_real
+    arr = lambda ps: (ctypes.c_void_p * n)(*[p or None for p in ps])
+    pu, psc, psh, py = (arr([u.data_ptr() for u in us]), arr([_lib.ptr(c.scale) for c in convs]), arr([_lib.ptr(c.shift) for c in convs]),
+                        arr([out.data_ptr()] * n))          # (host arrays: alive until the call returns)
+    nws = lib.sgv3d_conv2d_winograd4_multi_workspace_bytes(n, ctypes.addressof(descs))
+    ws = torch.empty(max(nws, 16), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device), prof("conv_wino4_x3_multi", flops, nbytes):
+        rc = lib.sgv3d_conv2d_winograd4_forward_multi(n, ctypes.addressof(descs), x.data_ptr(), ctypes.addressof(pu), ctypes.addressof(psc),
+                                                      ctypes.addressof(psh), ctypes.addressof(py), ws.data_ptr(), nws, _st(x))
+    _lib.check(rc, "sgv3d_conv2d_winograd4_forward_multi")
+    return out
+
+
+def wino4_multi_choice(convs, x, out, y_coffs, training=False):
+    """The f32x3 tiles to run ``wino4_multi`` with, or None when the per-layer calls are the way (the group is not covered, a layer's
+    choice for this input is not an f32x3 F(4x4) tile without split-K -- or not known yet: the first frame runs per layer -- or the
+    measurement said so).  Measured once per group and input shape against the per-layer calls and kept in the tune DB under a
+    ``pair|wino4multi|`` signature as [multi or not, 0].  The fixed rule (SGV3D_NO_AUTOTUNE, deterministic mode, a capture that meets
+    a new signature): the multi launch wherever it is covered."""
+    if not wino4_multi_eligible(convs, x, out, y_coffs, training):
+        return None
+    picks = [_wino4_sibling_choice(c, x) for c in convs]
+    if any(t not in WINO4_X3_TILES or sk != 1 for t, sk in picks):
+        return None
+    tiles = tuple(t for t, _ in picks)
+    sig = wino4_multi_signature(convs, x)
+    hit = tune_lookup(sig, x.device)
+    if hit is not None:
+        return tiles if int(hit[0]) else None
+    if not tune_may_measure():
+        return tiles
+    TUNE_STATS["measured"] += 1
+
+    def separate():
+        for c, o, t in zip(convs, y_coffs, tiles):
+            c(x, out, y_coff=o, tile=t, split_k=1)
+    t0, _, t1 = tune_best_of(sig, x.device, separate, [(1, lambda: wino4_multi(convs, x, out, y_coffs, tiles))])
+    on = t1 < t0
+    tune_record(sig, [1 if on else 0, 0])
+    return tiles if on else None
+
 
 # fp32 path: the kernel == stride transposed convolutions of the SECONDFPN necks on the f32x3 pointwise kernel (csrc/conv_pw_x3.hip
 # MODE 4: a 1x1 GEMM with ks * ks * cout columns and the transposed-conv scatter in its epilogue) instead of the f32 MFMA

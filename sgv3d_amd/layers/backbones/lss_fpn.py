@@ -120,8 +120,17 @@ class ASPP(HipModule):
                 hip_ops.broadcast_channels(x5, cat, y_coff=4 * mid)
 
         def conv_branches():
-            for i, m in enumerate((self.aspp1, self.aspp2, self.aspp3, self.aspp4)):
-                m.hip_state(x.device)(x, cat, y_coff=i * mid)
+            convs = [m.hip_state(x.device) for m in (self.aspp1, self.aspp2, self.aspp3, self.aspp4)]
+            convs[0](x, cat, y_coff=0)
+            # the three dilated 3x3 branches read the same x: one input-transform and one output-transform launch for all three
+            # where their choices are f32x3 F(4x4) tiles (hip_ops.wino4_multi_choice), else the three per-layer calls
+            offs = [mid, 2 * mid, 3 * mid]
+            tiles = hip_ops.wino4_multi_choice(convs[1:], x, cat, offs, training=self.training)
+            if tiles is not None:
+                hip_ops.wino4_multi(convs[1:], x, cat, offs, tiles)
+            else:
+                for c, o in zip(convs[1:], offs):
+                    c(x, cat, y_coff=o)
         hip_ops.run_parallel(x.device, (conv_branches, pooled_branch))
         if fold:
             return s['conv1_head'](cat, shift=folded[0].view(-1), out_dtype=x.dtype)
