@@ -1684,6 +1684,49 @@ int sgv3d_layernorm_bf16out(long long rows, int channels, const float *x, const 
 int sgv3d_gelu_bf16(long long n, const void *x, void *y, void *stream);
 
 /* ================================================================================================
+ * Training the encoder in bf16 mode (csrc/vit_grad_bf16.hip, hip_ops.VIT_TRAIN_BF16): the adjoints of the bf16 entries above.
+ * bf16 tensor pointers are void *.  Vector stores only, no float atomics, a fixed summation order: repeatable bit for bit and
+ * graph-capturable.  Every argument is checked on the host before any launch (SGV3D_EINVAL by name, SGV3D_ENOSPACE for a short
+ * workspace, with nothing written).
+ * ================================================================================================ */
+
+/* sgv3d_vit_attention_bf16 that also writes lse [batch, heads, height, width] (f32, natural-log units): (m + log2 l) ln 2 with m the
+ * row maximum in units of log2 and l the kernel's own row sum over the ROUNDED P.  The same kernel body: `out` is bit for bit what
+ * sgv3d_vit_attention_bf16 writes.  Rejects what that entry rejects, and a null or misaligned lse. */
+int sgv3d_vit_attention_bf16_lse(const sgv3d_vit_attn_desc *desc, const void *qkv, const float *pad_qkv, const float *rel_pos_h,
+                                 const float *rel_pos_w, void *out, float *lse, void *stream);
+
+/* The adjoint of sgv3d_vit_attention_bf16, with the semantics of sgv3d_vit_attention_backward (windows in the un-partitioned map,
+ * padding slots as keys but never as queries, the unscaled q in the relative-position terms, dpad_qkv with a zero q part).
+ *   qkv, out, dout   bf16, the forward's tensors and the upstream gradient     dqkv   bf16 [batch, height, width, 3 * heads * head_dim]
+ *   lse              f32, what sgv3d_vit_attention_bf16_lse wrote              pad_qkv, rel_pos_h, rel_pos_w   f32 (rounded on the way in)
+ *   dpad_qkv [3 * heads * head_dim], drel_pos_h, drel_pos_w   f32; required exactly when pad_qkv / the tables are given
+ * S is formed as the forward forms it (bf16 operands, the same k-step order, f32 scale, f32 T_h + T_w from the bf16 q and the
+ * bf16-rounded tables), P = exp2(S - lse) in f32.  The five products S, dP = dO V^T, dV += P^T dO, dK += dS^T Q, dQ += dS K run on
+ * v_mfma_f32_16x16x32_bf16 with f32 accumulation; P and dS = P (dP - delta) are rounded to bf16 once as MFMA operands;
+ * delta = dO . O is an f32 sum of the stored bf16 values; the softmax scale multiplies the f32 accumulators of dQ and dK.  A_h, A_w,
+ * their products with q and with the (bf16-rounded) tables, and the padding sums are f32 in the f32 adjoint's fixed order.  dqkv is
+ * rounded to bf16 once.  Nothing of size tokens x keys is stored.
+ * Rejected by name: what sgv3d_vit_attention_bf16 rejects, a null qkv / out / lse / dout / dqkv, gradient pointers that do not
+ * match pad_qkv / the tables, a pointer that is not 16-byte aligned, dqkv overlapping qkv, out or dout.
+ * sgv3d_vit_attention_bf16_backward_workspace_bytes is 0 for a descriptor the call would reject, and covers the call with tables. */
+size_t sgv3d_vit_attention_bf16_backward_workspace_bytes(const sgv3d_vit_attn_desc *desc);
+int sgv3d_vit_attention_bf16_backward(const sgv3d_vit_attn_desc *desc, const void *qkv, const float *pad_qkv, const float *rel_pos_h,
+                                      const float *rel_pos_w, const void *out, const float *lse, const void *dout, void *dqkv,
+                                      float *dpad_qkv, float *drel_pos_h, float *drel_pos_w, void *workspace, size_t workspace_bytes,
+                                      void *stream);
+
+/* sgv3d_layernorm_backward with a bf16 upstream gradient dy [rows, channels] (what the bf16 data gradient of qkv / lin1 writes): the
+ * same kernels on the widened dy, so bitwise sgv3d_layernorm_backward on dy as f32.  x, dx, dweight, dbias are f32; the workspace
+ * is sgv3d_layernorm_backward_workspace_bytes. */
+int sgv3d_layernorm_backward_bf16dy(long long rows, int channels, const float *x, const float *weight, float eps, const void *dy,
+                                    float *dx, float *dweight, float *dbias, void *workspace, size_t workspace_bytes, void *stream);
+
+/* sgv3d_gelu_backward on n bf16 values: the f32 formula on the widened x and dy, rounded once (RNE): bitwise the f32 entry on the
+ * widened inputs followed by a cast.  dx may be x or dy; any other overlap is rejected. */
+int sgv3d_gelu_backward_bf16(long long n, const void *x, const void *dy, void *dx, void *stream);
+
+/* ================================================================================================
  * SAM's prompt encoder and mask decoder (csrc/sam_decoder.hip): box prompts to class masks, inference only, f32.
  * Linear layers, the two transposed convolutions, LayerNorm and GELU run through sgv3d_conv2d_forward, sgv3d_layernorm and
  * sgv3d_gelu; these entries are the rest.  Every argument is checked on the host before any HIP call.  Vector stores only, no

@@ -284,6 +284,11 @@ _PROTOS = {
     "sgv3d_vit_attention_bf16": (c_int, [ctypes.POINTER(VitAttnDesc)] + [c_void_p] * 6),
     "sgv3d_layernorm_bf16out": (c_int, [c_ll, c_int] + [c_void_p] * 3 + [ctypes.c_float, c_void_p, c_void_p]),
     "sgv3d_gelu_bf16": (c_int, [c_ll, c_void_p, c_void_p, c_void_p]),
+    "sgv3d_vit_attention_bf16_lse": (c_int, [ctypes.POINTER(VitAttnDesc)] + [c_void_p] * 7),
+    "sgv3d_vit_attention_bf16_backward_workspace_bytes": (c_size_t, [ctypes.POINTER(VitAttnDesc)]),
+    "sgv3d_vit_attention_bf16_backward": (c_int, [ctypes.POINTER(VitAttnDesc)] + [c_void_p] * 12 + [c_size_t, c_void_p]),
+    "sgv3d_layernorm_backward_bf16dy": (c_int, [c_ll, c_int, c_void_p, c_void_p, ctypes.c_float] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "sgv3d_gelu_backward_bf16": (c_int, [c_ll] + [c_void_p] * 4),
     "sgv3d_sam_attention_workspace_bytes": (c_size_t, [ctypes.POINTER(SamAttnDesc)]),
     "sgv3d_sam_attention": (c_int, [ctypes.POINTER(SamAttnDesc)] + [c_void_p] * 5 + [c_size_t, c_void_p]),
     "sgv3d_sam_prompt_tokens": (c_int, [c_int] * 4 + [c_void_p] * 8),

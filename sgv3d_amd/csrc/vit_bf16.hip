@@ -75,6 +75,7 @@ struct AttnParams {
     const __bf16 *qkv;
     const float *pad, *rh, *rw;
     __bf16 *out;
+    float *lse;                   // the lse entry only: [B, nH, H, W], natural-log units
 };
 
 template <int HD>
@@ -88,8 +89,10 @@ constexpr float kLog2e = 1.44269504088896341f;
 
 // VEC: win_w % 4 == 0, so the four consecutive slots of a lane share kh and are four consecutive kw: one T_h read and one 16-byte
 // T_w read per four scores (tw_ld is a multiple of 4 then)
-template <int HD, int QW, bool VEC>
-__global__ __launch_bounds__(kBlock) void vit_attention_bf16_kernel(AttnParams p) {
+// LSE: also lse = (m + log2 l) ln 2 of every query, l the row sum over the rounded P (sgv3d_vit_attention_bf16_lse); `out` is
+// the same instruction stream either way
+template <int HD, int QW, bool VEC, bool LSE>
+__device__ __forceinline__ void vit_attention_bf16_body(const AttnParams &p) {
     constexpr int QT = 64 * QW;          // queries per workgroup
     constexpr int NK = (HD + 31) / 32;   // k-steps of Q K^T
     constexpr int ND = HD / 16;          // accumulators of O^T per query block
@@ -349,12 +352,31 @@ __global__ __launch_bounds__(kBlock) void vit_attention_bf16_kernel(AttnParams p
                 for (int r = 0; r < 4; ++r) o[r] = (__bf16)(O[qb][db][r] / sum);
                 *reinterpret_cast<bf16x4 *>(dst + 16 * db) = o;
             }
+            if (LSE && g == 0)
+                p.lse[(((size_t)wg.b * p.nH + head) * p.H + oh) * (size_t)p.W + ow] = (m[qb] + log2f(sum)) * 0.69314718055994530942f;
         }
     }
 }
 
 template <int HD, int QW, bool VEC>
+__global__ __launch_bounds__(kBlock) void vit_attention_bf16_kernel(AttnParams p) {
+    vit_attention_bf16_body<HD, QW, VEC, false>(p);
+}
+
+template <int HD, int QW, bool VEC>
+__global__ __launch_bounds__(kBlock) void vit_attention_bf16_lse_kernel(AttnParams p) {
+    vit_attention_bf16_body<HD, QW, VEC, true>(p);
+}
+
+template <int HD, int QW, bool VEC>
 int launch_attention(const AttnParams &p, int blocks, size_t lds_bytes, hipStream_t stream) {
+    if (p.lse) {
+        static PerDeviceSize state_lse;
+        if (!ensure_dynamic_lds(reinterpret_cast<const void *>(vit_attention_bf16_lse_kernel<HD, QW, VEC>), lds_bytes, state_lse))
+            return fail(SGV3D_ELAUNCH, "vit_attention_bf16_lse: cannot reserve %zu bytes of LDS", lds_bytes);
+        hipLaunchKernelGGL((vit_attention_bf16_lse_kernel<HD, QW, VEC>), dim3(blocks), dim3(kBlock), lds_bytes, stream, p);
+        return check_launch("vit_attention_bf16_lse_kernel");
+    }
     static PerDeviceSize state;
     if (!ensure_dynamic_lds(reinterpret_cast<const void *>(vit_attention_bf16_kernel<HD, QW, VEC>), lds_bytes, state))
         return fail(SGV3D_ELAUNCH, "vit_attention_bf16: cannot reserve %zu bytes of LDS", lds_bytes);
@@ -408,16 +430,16 @@ __global__ __launch_bounds__(kBlock) void gelu_bf16_kernel(long long n8, int tai
 
 }  // namespace
 
-extern "C" int sgv3d_vit_attention_bf16(const sgv3d_vit_attn_desc *desc, const void *qkv, const float *pad_qkv, const float *rel_pos_h,
-                                        const float *rel_pos_w, void *out, void *stream) {
-    const int rc = check_attn_desc("vit_attention_bf16", desc, 8);
+// sgv3d_vit_attention_bf16 (lse null) and sgv3d_vit_attention_bf16_lse: one set of checks, one launch geometry
+static int vit_attention_bf16_impl(const char *who, const sgv3d_vit_attn_desc *desc, const void *qkv, const float *pad_qkv,
+                                   const float *rel_pos_h, const float *rel_pos_w, void *out, float *lse, void *stream) {
+    const int rc = check_attn_desc(who, desc, 8);
     if (rc != SGV3D_OK) return rc;
     const sgv3d_vit_attn_desc &d = *desc;
-    SGV3D_REQUIRE((rel_pos_h == nullptr) == (rel_pos_w == nullptr),
-                  "vit_attention_bf16: rel_pos_h and rel_pos_w must be given together or not at all");
-    SGV3D_REQUIRE(qkv && out, "vit_attention_bf16: null qkv or out");
+    SGV3D_REQUIRE((rel_pos_h == nullptr) == (rel_pos_w == nullptr), "%s: rel_pos_h and rel_pos_w must be given together or not at all", who);
+    SGV3D_REQUIRE(qkv && out, "%s: null qkv or out", who);
     SGV3D_REQUIRE(aligned16(qkv) && aligned16(out) && aligned16(pad_qkv) && aligned16(rel_pos_h) && aligned16(rel_pos_w),
-                  "vit_attention_bf16: qkv, pad_qkv, rel_pos_h, rel_pos_w and out must be 16-byte aligned");
+                  "%s: qkv, pad_qkv, rel_pos_h, rel_pos_w and out must be 16-byte aligned", who);
     AttnParams p;
     fill_window(p, d);
     const bool rel = rel_pos_h != nullptr;
@@ -426,6 +448,7 @@ extern "C" int sgv3d_vit_attention_bf16(const sgv3d_vit_attn_desc *desc, const v
     p.tw_ld = vec ? d.win_w + 4 : odd_ld(rel, d.win_w);
     p.scale2 = softmax_scale(d.head_dim) * kLog2e;
     p.qkv = static_cast<const __bf16 *>(qkv), p.pad = pad_qkv, p.rh = rel_pos_h, p.rw = rel_pos_w, p.out = static_cast<__bf16 *>(out);
+    p.lse = lse;
     const size_t kv_bytes = d.head_dim == 32 ? AttnGeom<32>::kv_bytes : d.head_dim == 64 ? AttnGeom<64>::kv_bytes : AttnGeom<80>::kv_bytes;
     const size_t t_bytes = sizeof(float) * (size_t)(p.th_ld + p.tw_ld);      // per query
     // 32 queries per wave (a K / V fragment read feeds two MFMAs) where a window has more than 64 queries and two workgroups
@@ -435,13 +458,25 @@ extern "C" int sgv3d_vit_attention_bf16(const sgv3d_vit_attn_desc *desc, const v
     p.nqt = cdiv(p.T, qtile);
     const size_t lds_bytes = kv_bytes + (size_t)qtile * t_bytes;
     const long long blocks = (long long)d.batch * d.heads * p.nwy * p.nwx * p.nqt;
-    SGV3D_REQUIRE(blocks < (1LL << 31), "vit_attention_bf16: too many workgroups");
+    SGV3D_REQUIRE(blocks < (1LL << 31), "%s: too many workgroups", who);
     hipStream_t s = as_stream(stream);
     switch (d.head_dim) {
         case 32: return launch_attention_hd<32>(p, wide, vec, (int)blocks, lds_bytes, s);
         case 64: return launch_attention_hd<64>(p, wide, vec, (int)blocks, lds_bytes, s);
         default: return launch_attention_hd<80>(p, wide, vec, (int)blocks, lds_bytes, s);
     }
+}
+
+extern "C" int sgv3d_vit_attention_bf16(const sgv3d_vit_attn_desc *desc, const void *qkv, const float *pad_qkv, const float *rel_pos_h,
+                                        const float *rel_pos_w, void *out, void *stream) {
+    return vit_attention_bf16_impl("vit_attention_bf16", desc, qkv, pad_qkv, rel_pos_h, rel_pos_w, out, nullptr, stream);
+}
+
+extern "C" int sgv3d_vit_attention_bf16_lse(const sgv3d_vit_attn_desc *desc, const void *qkv, const float *pad_qkv, const float *rel_pos_h,
+                                            const float *rel_pos_w, void *out, float *lse, void *stream) {
+    SGV3D_REQUIRE(lse, "vit_attention_bf16_lse: null lse");
+    SGV3D_REQUIRE(aligned16(lse), "vit_attention_bf16_lse: lse must be 16-byte aligned");
+    return vit_attention_bf16_impl("vit_attention_bf16_lse", desc, qkv, pad_qkv, rel_pos_h, rel_pos_w, out, lse, stream);
 }
 
 extern "C" int sgv3d_layernorm_bf16out(long long rows, int channels, const float *x, const float *weight, const float *bias, float eps,

@@ -1,6 +1,6 @@
-// What the three ViT sources (vit.hip, vit_bf16.hip, vit_grad.hip) must agree on bit for bit, each defined once: the descriptor
-// checks and the window geometry of the attention entries, the LayerNorm row statistics, the erf term of GELU, and the
-// f32 MFMA operand code for a head dimension split into 64-, 32- and 16-wide parts.  gfx950 only.
+// What the four ViT sources (vit.hip, vit_bf16.hip, vit_grad.hip, vit_grad_bf16.hip) must agree on bit for bit, each defined
+// once: the descriptor checks and the window geometry of the attention entries, the LayerNorm row statistics, the erf term of
+// GELU, and the f32 MFMA operand code for a head dimension split into 64-, 32- and 16-wide parts.  gfx950 only.
 #pragma once
 #include <math.h>
 

@@ -514,21 +514,31 @@ int launch_bwd_hd(const BwdParams &p, long long blocks, size_t lds_bytes, hipStr
 // ------------------------------------------------------------------------------------------------
 // LayerNorm backward
 // ------------------------------------------------------------------------------------------------
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// four values of dy as f32: the f32 tensor's own, or the bf16 tensor's widened (exact), so that sgv3d_layernorm_backward_bf16dy
+// does the arithmetic of sgv3d_layernorm_backward on dy.float()
+__device__ __forceinline__ f32x4 widen4(const f32x4 v) { return v; }
+__device__ __forceinline__ f32x4 widen4(const bf16x4 v) { return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]}; }
+
 // One wave per row: the forward's mean and rstd (ln_row_stats), the two row sums of the gradient in f64, dx; the row's mean and rstd
-// go to the workspace for the weight / bias partials.
+// go to the workspace for the weight / bias partials.  DY4: f32x4 or bf16x4.
+template <class DY4>
 __global__ __launch_bounds__(kBlock) void layernorm_bwd_dx_kernel(long long rows, int c4, const f32x4 *__restrict__ x,
-                                                                  const f32x4 *__restrict__ weight, float eps, const f32x4 *dy, f32x4 *dx,
+                                                                  const f32x4 *__restrict__ weight, float eps, const DY4 *dy, f32x4 *dx,
                                                                   double *stats) {
     const int lane = threadIdx.x & 63;
     const long long row = (long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const f32x4 *xr = x + row * c4, *gr = dy + row * c4;
+    const f32x4 *xr = x + row * c4;
+    const DY4 *gr = dy + row * c4;
     f32x4 *dr = dx + row * c4;
     const double inv_c = 1.0 / (4.0 * (double)c4);
     const LnStats st = ln_row_stats(xr, c4, lane, eps);
     double s1 = 0.0, s2 = 0.0;
     for (int i = lane; i < c4; i += 64) {
-        const f32x4 v = xr[i], w = weight[i], d = gr[i];
+        const f32x4 v = xr[i], w = weight[i], d = widen4(gr[i]);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const double gk = (double)d[k] * (double)w[k];
@@ -539,7 +549,7 @@ __global__ __launch_bounds__(kBlock) void layernorm_bwd_dx_kernel(long long rows
     }
     const double m1 = wave_sum(s1) * inv_c, m2 = wave_sum(s2) * inv_c;
     for (int i = lane; i < c4; i += 64) {
-        const f32x4 v = xr[i], w = weight[i], d = gr[i];
+        const f32x4 v = xr[i], w = weight[i], d = widen4(gr[i]);
         f32x4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -554,9 +564,10 @@ __global__ __launch_bounds__(kBlock) void layernorm_bwd_dx_kernel(long long rows
     }
 }
 
-// partial[chunk][2][C] (f64): a chunk of kLnChunk rows, one thread per channel, rows in order
+// partial[chunk][2][C] (f64): a chunk of kLnChunk rows, one thread per channel, rows in order.  DY: float or __bf16.
+template <class DY>
 __global__ __launch_bounds__(kBlock) void layernorm_bwd_partial_kernel(long long rows, int C, const float *__restrict__ x,
-                                                                       const float *__restrict__ dy, const double *__restrict__ stats,
+                                                                       const DY *__restrict__ dy, const double *__restrict__ stats,
                                                                        double *partial) {
     const int c = blockIdx.y * kBlock + threadIdx.x;
     if (c >= C) return;
@@ -564,7 +575,7 @@ __global__ __launch_bounds__(kBlock) void layernorm_bwd_partial_kernel(long long
     double sw = 0.0, sb = 0.0;
     for (long long r = r0; r < r1; ++r) {
         const float xh = ln_xhat(x[r * C + c], LnStats{stats[2 * r], (float)stats[2 * r + 1]});
-        const double d = (double)dy[r * C + c];
+        const double d = (double)(float)dy[r * C + c];
         sw += d * (double)xh;
         sb += d;
     }
@@ -604,6 +615,19 @@ __global__ __launch_bounds__(kBlock) void gelu_bwd_kernel(long long n4, int tail
         reinterpret_cast<f32x4 *>(dx)[i] = o;
     }
     if (i < tail) dx[4 * n4 + i] = gelu_grad1(x[4 * n4 + i], dy[4 * n4 + i]);
+}
+
+// bf16 tensors: gelu_grad1 on the widened values, rounded once (RNE).  Every thread reads its values before it writes: in place is fine.
+__global__ __launch_bounds__(kBlock) void gelu_bwd_bf16_kernel(long long n8, int tail, const __bf16 *x, const __bf16 *dy, __bf16 *dx) {
+    const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
+    if (i < n8) {
+        const bf16x8 v = reinterpret_cast<const bf16x8 *>(x)[i], d = reinterpret_cast<const bf16x8 *>(dy)[i];
+        bf16x8 o;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) o[k] = (__bf16)gelu_grad1((float)v[k], (float)d[k]);
+        reinterpret_cast<bf16x8 *>(dx)[i] = o;
+    }
+    if (i < tail) dx[8 * n8 + i] = (__bf16)gelu_grad1((float)x[8 * n8 + i], (float)dy[8 * n8 + i]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -737,38 +761,57 @@ extern "C" size_t sgv3d_layernorm_backward_workspace_bytes(long long rows, int c
     return sizeof(double) * (size_t)(2 * rows + 2 * chunks * channels);
 }
 
-extern "C" int sgv3d_layernorm_backward(long long rows, int channels, const float *x, const float *weight, float eps, const float *dy,
-                                        float *dx, float *dweight, float *dbias, void *workspace, size_t workspace_bytes, void *stream) {
-    SGV3D_REQUIRE(rows > 0 && channels > 0, "layernorm_backward: non-positive size (rows %lld, channels %d)", rows, channels);
-    SGV3D_REQUIRE(channels % 4 == 0, "layernorm_backward: channels %d is not a multiple of 4", channels);
-    SGV3D_REQUIRE(x && weight && dy && dx && dweight && dbias, "layernorm_backward: null pointer");
-    SGV3D_REQUIRE(eps >= 0.f, "layernorm_backward: negative eps");
+// sgv3d_layernorm_backward (DY = float) and sgv3d_layernorm_backward_bf16dy (DY = __bf16): one set of checks, the same three launches
+template <class DY, class DY4>
+static int layernorm_backward_impl(const char *who, long long rows, int channels, const float *x, const float *weight, float eps,
+                                   const DY *dy, float *dx, float *dweight, float *dbias, void *workspace, size_t workspace_bytes,
+                                   void *stream) {
+    SGV3D_REQUIRE(rows > 0 && channels > 0, "%s: non-positive size (rows %lld, channels %d)", who, rows, channels);
+    SGV3D_REQUIRE(channels % 4 == 0, "%s: channels %d is not a multiple of 4", who, channels);
+    SGV3D_REQUIRE(x && weight && dy && dx && dweight && dbias, "%s: null pointer", who);
+    SGV3D_REQUIRE(eps >= 0.f, "%s: negative eps", who);
     SGV3D_REQUIRE(aligned16(x) && aligned16(weight) && aligned16(dy) && aligned16(dx) && aligned16(dweight) && aligned16(dbias) &&
                       aligned16(workspace),
-                  "layernorm_backward: pointers must be 16-byte aligned");
+                  "%s: pointers must be 16-byte aligned", who);
     // the weight / bias partials read x and dy after dx has been written
     const unsigned long long span = 4ULL * (unsigned long long)rows * (unsigned long long)channels;
-    SGV3D_REQUIRE(!overlaps(dx, x, span) && !overlaps(dx, dy, span), "layernorm_backward: dx must not overlap x or dy");
+    // (dy spans sizeof(DY) bytes per value: for the f32 dy the same test as for x)
+    const unsigned long long dy_span = sizeof(DY) * (unsigned long long)rows * (unsigned long long)channels;
+    const uintptr_t pdx = reinterpret_cast<uintptr_t>(dx), pdy = reinterpret_cast<uintptr_t>(dy);
+    SGV3D_REQUIRE(!overlaps(dx, x, span) && !(pdx < pdy + dy_span && pdy < pdx + span), "%s: dx must not overlap x or dy", who);
     const long long blocks = (rows + kBlock / 64 - 1) / (kBlock / 64);
     const long long chunks = (rows + kLnChunk - 1) / kLnChunk;
-    SGV3D_REQUIRE(blocks < (1LL << 31), "layernorm_backward: too many rows");
+    SGV3D_REQUIRE(blocks < (1LL << 31), "%s: too many rows", who);
     const size_t need = sgv3d_layernorm_backward_workspace_bytes(rows, channels);
     if (!workspace || workspace_bytes < need)
-        return fail(SGV3D_ENOSPACE, "layernorm_backward: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+        return fail(SGV3D_ENOSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace ? workspace_bytes : (size_t)0, need);
     double *stats = static_cast<double *>(workspace), *partial = stats + 2 * rows;
     hipStream_t s = as_stream(stream);
-    hipLaunchKernelGGL(layernorm_bwd_dx_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, s, rows, channels / 4,
+    hipLaunchKernelGGL(layernorm_bwd_dx_kernel<DY4>, dim3((unsigned)blocks), dim3(kBlock), 0, s, rows, channels / 4,
                        reinterpret_cast<const f32x4 *>(x), reinterpret_cast<const f32x4 *>(weight), eps,
-                       reinterpret_cast<const f32x4 *>(dy), reinterpret_cast<f32x4 *>(dx), stats);
+                       reinterpret_cast<const DY4 *>(dy), reinterpret_cast<f32x4 *>(dx), stats);
     int r = check_launch("layernorm_bwd_dx_kernel");
     if (r != SGV3D_OK) return r;
-    hipLaunchKernelGGL(layernorm_bwd_partial_kernel, dim3((unsigned)chunks, (unsigned)cdiv(channels, kBlock)), dim3(kBlock), 0, s, rows,
+    hipLaunchKernelGGL(layernorm_bwd_partial_kernel<DY>, dim3((unsigned)chunks, (unsigned)cdiv(channels, kBlock)), dim3(kBlock), 0, s, rows,
                        channels, x, dy, stats, partial);
     r = check_launch("layernorm_bwd_partial_kernel");
     if (r != SGV3D_OK) return r;
     hipLaunchKernelGGL(layernorm_bwd_finish_kernel, dim3((unsigned)cdiv(channels, kBlock)), dim3(kBlock), 0, s, (int)chunks, channels,
                        partial, dweight, dbias);
     return check_launch("layernorm_bwd_finish_kernel");
+}
+
+extern "C" int sgv3d_layernorm_backward(long long rows, int channels, const float *x, const float *weight, float eps, const float *dy,
+                                        float *dx, float *dweight, float *dbias, void *workspace, size_t workspace_bytes, void *stream) {
+    return layernorm_backward_impl<float, f32x4>("layernorm_backward", rows, channels, x, weight, eps, dy, dx, dweight, dbias, workspace,
+                                                 workspace_bytes, stream);
+}
+
+extern "C" int sgv3d_layernorm_backward_bf16dy(long long rows, int channels, const float *x, const float *weight, float eps, const void *dy,
+                                               float *dx, float *dweight, float *dbias, void *workspace, size_t workspace_bytes,
+                                               void *stream) {
+    return layernorm_backward_impl<__bf16, bf16x4>("layernorm_backward_bf16dy", rows, channels, x, weight, eps,
+                                                   static_cast<const __bf16 *>(dy), dx, dweight, dbias, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sgv3d_gelu_backward(long long n, const float *x, const float *dy, float *dx, void *stream) {
@@ -780,6 +823,22 @@ extern "C" int sgv3d_gelu_backward(long long n, const float *x, const float *dy,
     SGV3D_REQUIRE(blocks < (1LL << 31), "gelu_backward: too many values");
     hipLaunchKernelGGL(gelu_bwd_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), n4, (int)(n - 4 * n4), x, dy, dx);
     return check_launch("gelu_bwd_kernel");
+}
+
+extern "C" int sgv3d_gelu_backward_bf16(long long n, const void *x, const void *dy, void *dx, void *stream) {
+    SGV3D_REQUIRE(n > 0, "gelu_backward_bf16: non-positive count %lld", n);
+    SGV3D_REQUIRE(x && dy && dx, "gelu_backward_bf16: null pointer");
+    SGV3D_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(dx), "gelu_backward_bf16: pointers must be 16-byte aligned");
+    // in place (dx the same tensor as x or dy) is allowed; a shifted overlap is not: a thread would read what another has written
+    const unsigned long long span = 2ULL * (unsigned long long)n;
+    SGV3D_REQUIRE((dx == x || !overlaps(dx, x, span)) && (dx == dy || !overlaps(dx, dy, span)),
+                  "gelu_backward_bf16: dx must be x, dy or a tensor that overlaps neither");
+    const long long n8 = n / 8;
+    const long long blocks = (n8 + kBlock) / kBlock;    // at least one: its first threads take the tail
+    SGV3D_REQUIRE(blocks < (1LL << 31), "gelu_backward_bf16: too many values");
+    hipLaunchKernelGGL(gelu_bwd_bf16_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, as_stream(stream), n8, (int)(n - 8 * n8),
+                       static_cast<const __bf16 *>(x), static_cast<const __bf16 *>(dy), static_cast<__bf16 *>(dx));
+    return check_launch("gelu_bwd_bf16_kernel");
 }
 
 extern "C" int sgv3d_resize_bilinear_backward(int batch, int h, int w, int channels, int crop_h, int crop_w, int out_h, int out_w,

@@ -92,6 +92,11 @@ TRAIN_BF16_STORAGE = _os.environ.get("SGV3D_TRAIN_BF16_STORAGE", "0") not in (""
 # attention runs on the bf16 matrix cores (csrc/vit_bf16.hip); the residual stream, the patch embedding and the neck keep f32 tensors.
 # Takes effect only where vit_bf16_active() says so; off, or not covered: the f32-tensor path of the compute mode, bit for bit.
 VIT_BF16 = _os.environ.get("SGV3D_VIT_BF16", "0") not in ("", "0")
+# TRAINING the SAM ViT encoder in bf16 mode (SGV3D_VIT_TRAIN_BF16=1, default off): sgv3d_amd/vit_train.py runs the launches of the bf16
+# inference mode above (bf16 tensors between the two residual adds of a Block, saved as they are) and their adjoints: attention on the
+# bf16 matrix cores (csrc/vit_grad_bf16.hip), bf16-tensor data and weight gradients of the linear layers.  Takes effect only where
+# vit_train_bf16_active() says so; off, or not covered: the f32-tensor training path, bit for bit.
+VIT_TRAIN_BF16 = _os.environ.get("SGV3D_VIT_TRAIN_BF16", "0") not in ("", "0")
 # 1x1 layers with unpadded channel counts read the OIHW weight tensor itself as their packed weights (diagnostic: 0 packs a copy)
 ALIAS_1X1_WEIGHTS = _os.environ.get("SGV3D_ALIAS_1X1_WEIGHTS", "1") != "0"
 # True (SGV3D_F32X3=1): the implicit-GEMM layers compute float32-accurate products on the bf16 matrix cores -- every
@@ -389,6 +394,14 @@ def vit_train_covers(dim, num_heads):
     if dim <= 0 or num_heads <= 0 or dim % num_heads or dim % 4:
         return False
     return dim // num_heads in (32, 64, 80)
+
+
+def vit_train_bf16_active(dim, num_heads, mlp_dim=None):
+    """VIT_TRAIN_BF16 in bf16 compute mode (MFMA_BF16, not the f32x3 split) with bf16 weight gradients (TRAIN_BF16_WGRAD) on a Block
+    that both the bf16 kernels (vit_bf16_covers) and the training forward (vit_train_covers) take; otherwise the f32-tensor training
+    path runs, silently, like the other coverage rules."""
+    return bool(VIT_TRAIN_BF16 and MFMA_BF16 and not MFMA_F32X3 and TRAIN_BF16_WGRAD and vit_bf16_covers(dim, num_heads, mlp_dim)
+                and vit_train_covers(dim, num_heads))
 
 
 def dice_covers(mode, num_classes):
