@@ -1131,6 +1131,45 @@ int sgv3d_dice_loss_backward(int batch, int num_classes, int pixels, const float
                              int activation, long long ignore_index, int use_ignore_index, double smooth, double eps,
                              const double *saved, const float *upstream, float *grad, void *stream);
 
+/* Embedding distillation (csrc/embed_distill.hip): SAM's image embedding as a target for the camera backbone's 1/16 assist map.
+ *   The warp is transform_with_M_bilinear (dataset/nusc_mv_det_dataset.py:351-385) in float64, per frame b with warped[b] != 0
+ *   and m = minv[b] = inv(M) row-major: output pixel (x, y) is the point (10x, 10y, 10); a = (m0 X + m1 Y) + m2 Z, likewise b and
+ *   c; u = a / c, v = b / c; the pixel is dead (all channels 0) where u < 0, u > w - 2, v < 0, v > h - 2 or where either is not a
+ *   number; else c0 = floor(u), r0 = floor(v), the horizontal blends ((c0 + 1) - u) I[r, c0] + (u - c0) I[r, c0 + 1] on rows r0 and
+ *   r0 + 1, the vertical blend ((r0 + 1) - v) f1 + (v - r0) f2, one rounding to float32.  A frame with warped[b] == 0 is copied
+ *   unchanged and has no dead pixel (the reference warps rectified frames only).
+ *   teacher, out f32 [B, h, w, C] NHWC, 16-byte aligned, not overlapping; minv f64 [B][9] and warped u8 [B] in device memory;
+ *   dead u8 [B, h, w] or NULL.  C % 4 == 0, h, w >= 2.  One launch, enqueue only. */
+int sgv3d_embed_warp(int batch, int h, int w, int channels, const float *teacher, const double *minv, const uint8_t *warped,
+                     float *out, uint8_t *dead, void *stream);
+/* HOST function: the same arithmetic over host pointers (CPU tests, sanitizer builds). */
+int sgv3d_embed_warp_host(int batch, int h, int w, int channels, const float *teacher, const double *minv, const uint8_t *warped,
+                          float *out, uint8_t *dead);
+
+/* loss = weight * sum d^2 / N with d = student - warp(teacher): F.mse_loss(gt_embeds, assist_features) * weight
+ * (exps/bevheight/dair-v2x/bev_height_lss_r50_864_1536_128x128.py:247-256) on the warp above, which is formed per pixel and
+ * never written.  student f32, element (b, c, p) at b*batch_stride + c*channel_stride + p*pixel_stride (floats, channel and
+ * pixel strides >= 1): the NCHW view of an NHWC buffer, a plain NCHW tensor, a batch slice.  minv and warped as above, or both
+ * NULL (no frame is warped).  d and d * d are float32, the sum float64 over a fixed grid of per-workgroup partials and a
+ * one-workgroup finish in a fixed order.  mask_dead 0: a dead pixel counts with target 0 and N = B C h w (the reference's
+ * composition); 1: dead pixels leave the sum and N, which is counted on the device with integer adds; N = 0 gives loss 0.
+ *   loss_out f32 [1]; saved f64 [2] = (N, 2 weight / N; 0 where N = 0), what backward needs.
+ *   backward: grad (addressed like student, every element of the view written once) = upstream[0] * float32(saved[1] * d);
+ *   upstream f32 [1] on the device, NULL = 1.  The warp is recomputed.  grad must not overlap teacher.
+ *   Three launches in all, no host wait, no float atomics: bitwise repeatable and capturable in a hipGraph.
+ *   workspace: sgv3d_embed_distill_workspace_bytes() bytes, 8-byte aligned.
+ *   Refused before any launch: sizes <= 0, h or w < 2, C % 4 != 0, a null pointer, minv without warped, bad strides, a
+ *   misaligned teacher, a non-finite weight, grad overlapping teacher (SGV3D_EINVAL); a short workspace (SGV3D_ENOSPACE). */
+size_t sgv3d_embed_distill_workspace_bytes(void);
+int sgv3d_embed_distill_forward(int batch, int channels, int h, int w, const float *student, long long batch_stride,
+                                long long channel_stride, long long pixel_stride, const float *teacher, const double *minv,
+                                const uint8_t *warped, double weight, int mask_dead, float *loss_out, double *saved,
+                                void *workspace, size_t workspace_bytes, void *stream);
+int sgv3d_embed_distill_backward(int batch, int channels, int h, int w, const float *student, long long batch_stride,
+                                 long long channel_stride, long long pixel_stride, const float *teacher, const double *minv,
+                                 const uint8_t *warped, int mask_dead, const double *saved, const float *upstream, float *grad,
+                                 void *stream);
+
 /* Adjoint of sgv3d_upsample_bilinear2x: dy f32 [B, 2H, 2W, C] -> dx f32 [B, H, W, C] (any C). */
 int sgv3d_upsample_bilinear2x_backward(int batch, int h, int w, int channels, const float *dy, float *dx, void *stream);
 

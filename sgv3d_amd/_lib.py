@@ -222,6 +222,13 @@ _PROTOS = {
                                         c_size_t, c_void_p]),
     "sgv3d_dice_loss_backward": (c_int, [c_int] * 3 + [c_void_p, c_ll, c_ll, c_ll, c_void_p, c_int, c_int, c_ll, c_int,
                                          ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sgv3d_embed_warp": (c_int, [c_int] * 4 + [c_void_p] * 6),
+    "sgv3d_embed_warp_host": (c_int, [c_int] * 4 + [c_void_p] * 5),
+    "sgv3d_embed_distill_workspace_bytes": (c_size_t, []),
+    "sgv3d_embed_distill_forward": (c_int, [c_int] * 4 + [c_void_p, c_ll, c_ll, c_ll, c_void_p, c_void_p, c_void_p,
+                                            ctypes.c_double, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "sgv3d_embed_distill_backward": (c_int, [c_int] * 4 + [c_void_p, c_ll, c_ll, c_ll, c_void_p, c_void_p, c_void_p, c_int,
+                                             c_void_p, c_void_p, c_void_p, c_void_p]),
     "sgv3d_upsample_bilinear2x_backward": (c_int, [c_int] * 4 + [c_void_p] * 3),
     "sgv3d_add_mul_sigmoid_backward": (c_int, [c_ll] + [c_void_p] * 6),
     "sgv3d_maxpool3x3s2_train_forward": (c_int, [c_int] * 4 + [c_void_p] * 4),

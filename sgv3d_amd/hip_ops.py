@@ -414,6 +414,12 @@ def dice_covers(mode, num_classes):
     return mode in ("binary", "multilabel") and c >= 1
 
 
+def embed_distill_covers(channels, h, w):
+    """Whether the embedding warp and distillation loss (csrc/embed_distill.hip) take this map: a lane owns a quad of channels
+    (16-byte accesses), and the bilinear warp needs two rows and two columns.  An uncovered shape raises before any launch."""
+    return int(channels) >= 4 and int(channels) % 4 == 0 and int(h) >= 2 and int(w) >= 2
+
+
 def sam_decoder_covers(transformer_dim, num_heads, downsample_rate=2):
     """Whether the SAM mask decoder's kernels take a two-way transformer of this shape: sgv3d_sam_attention has head dimensions 16
     and 32, so transformer_dim / num_heads (self-attention) and transformer_dim / downsample_rate / num_heads (the cross

@@ -43,6 +43,12 @@ ap.add_argument("--checkpoint", default=None, help="after the timed steps: time 
                 "back into the model and optimiser (sgv3d_amd/checkpoint.py)")
 ap.add_argument("--dice-weight", type=float, default=0.0, help="BSM configs: add dice_weight x DiceLoss('multiclass') to each semantic map's "
                 "focal loss (losses.SemanticSupervision); 0 = the focal loss alone")
+ap.add_argument("--distill-weight", type=float, default=0.0, help="LSSFPN configs: add distill_weight x mse(assist features, SAM embedding) "
+                "(losses.EmbedDistillation): the model is built with is_train_height, a random-weight SAM ViT-B teacher embeds "
+                "the batch's frames once ahead, and about half the frames carry a rectification whose embedding warp runs inside "
+                "the loss; 0 = nothing of this is built")
+ap.add_argument("--distill-mask-dead", action="store_true", help="with --distill-weight: pixels whose source lies outside the teacher's frame "
+                "leave the loss (EmbedDistillation(mask_dead=True)) instead of counting with target 0 as in the reference")
 args = ap.parse_args()
 
 hip_ops.DCN_FUSED_TRAIN = not args.no_fuse_dcn
@@ -58,10 +64,14 @@ if args.config == "cfg4":
     args.batch = 4
 bconf, hconf = {"cfg2": synthetic.r50_256_conf, "cfg4": synthetic.r50_256_conf, "cfg5": synthetic.bsm_r101_256_conf, "small": synthetic.small_conf}[args.config]()
 BSM = bool(bconf.get('is_bsm'))                 # cfg5: SGV3D BSM R101 with the semantic (SAM-mask) supervision
-if BSM:
+DISTILL = args.distill_weight != 0.0
+if DISTILL and BSM:
+    raise ValueError("--distill-weight: the BSM backbone has no assist layer (its is_train_height output is the semantic maps); "
+                     "use an LSSFPN config")
+if BSM or DISTILL:
     bconf = dict(bconf, is_train_height=True)
 torch.manual_seed(0)
-model = BEVHeight(bconf, hconf, is_train_height=BSM).to(dev).train()
+model = BEVHeight(bconf, hconf, is_train_height=BSM or DISTILL).to(dev).train()
 if args.no_fuse_lift_splat:
     model.backbone.fuse_lift_splat = False
 for m in model.modules():
@@ -78,6 +88,28 @@ if BSM:
     semantic = SemanticSupervision(8, dice_weight=args.dice_weight)
     gt_semantic = torch.randint(0, 7, (args.batch, 1) + tuple(bconf['final_dim']), dtype=torch.uint8,
                                 generator=torch.Generator().manual_seed(group.rank)).to(dev)
+if DISTILL:
+    import random
+    import numpy as np
+    from sgv3d_amd import distill, train_augment
+    from sgv3d_amd.layers.backbones.sam_encoder import build_sam_vit_b
+    from sgv3d_amd.losses import EmbedDistillation
+    rng_state = torch.get_rng_state()           # the teacher's random weights must not move the model's dropout stream
+    teacher = distill.SamTeacher(build_sam_vit_b(bconf['final_dim'], bconf['downsample_factor']).to(dev).eval(),
+                                 dict(final_dim=bconf['final_dim']), src_hw=(synthetic.H, synthetic.W))
+    torch.set_rng_state(rng_state)
+    frames = torch.randint(0, 256, (args.batch, synthetic.H, synthetic.W, 3), dtype=torch.uint8,
+                           generator=torch.Generator().manual_seed(group.rank)).to(dev)
+    embeds = teacher(frames).contiguous()       # once, ahead of the steps: the teacher sees the unaugmented frames
+    DISTILL_SEED = 2                            # about half the frames are rectified (1 of 2, 2 of 4, 4 of 8)
+    aug = train_augment.sample_params(args.batch, random.Random(DISTILL_SEED), np.random.RandomState(DISTILL_SEED))
+    cams = [dict(intrin=mats['intrin_mats'][b, 0, 0].cpu().numpy(), sensor2ego=mats['sensor2ego_mats'][b, 0, 0].cpu().numpy())
+            for b in range(args.batch)]
+    minv, warped = distill.embed_warp_matrices(cams, [train_augment.augment_camera(c, aug, i) for i, c in enumerate(cams)], aug,
+                                               teacher.scale)
+    minv, warped = torch.from_numpy(minv).to(dev), torch.from_numpy(warped).to(dev)
+    distillation = EmbedDistillation(args.distill_weight, mask_dead=args.distill_mask_dead)
+    del teacher, frames
 opt = DataParallelAdamW(model.parameters(), lr=reference_lr(args.batch, group.world), max_grad_norm=args.clip or None,
                         bucket_bytes=None if args.bucket_mib is None else args.bucket_mib << 20)   # broadcasts rank 0's parameters
 if not args.no_overlap:
@@ -87,12 +119,14 @@ nparam = sum(p.numel() for p in model.parameters())
 
 def forward_backward():
     preds = model(imgs, mats)
-    if BSM:                                     # exps/sgv3d/bsm_bev_height_lss_r101_864_1536_256x256.py:304-330
+    if BSM or DISTILL:                          # exps/sgv3d/bsm_bev_height_lss_r101_864_1536_256x256.py:304-330
         preds, img_preds = preds
     targets = model.get_targets(boxes, labels)
     loss = model.loss(targets, preds)
     if BSM:
         loss = loss + semantic(img_preds, gt_semantic) * 500
+    if DISTILL:                                 # exps/bevheight/dair-v2x/bev_height_lss_r50_864_1536_128x128.py:247-256
+        loss = loss + distillation(img_preds[0], embeds, minv, warped)
     if BW_EVENTS:
         BW_EVENTS[0].record()
     loss.backward()
@@ -162,7 +196,9 @@ out = {"metric": "training samples/s (forward + loss + backward + all-reduce + A
        "batch_per_gpu": args.batch, "global_batch": args.batch * group.world, "dtype": args.dtype,
        "world_size": group.dist.get_world_size() if group.dist is not None else 1, "backend": group.backend,
        "allreduce_bytes_per_step": 4 * sum(g.numel() for _, g, _ in opt.flat.buckets), "allreduce_buckets": len(opt.flat.buckets),
-       "allreduce_overlapped_with_backward": not args.no_overlap, "parameters": nparam, "loss": float(loss.detach()), "config": args.config, "dice_weight": args.dice_weight if BSM else None, "loss_trace": TRACE or None, "graph": bool(args.graph), "graph_replays": graphed.replays if args.graph else 0,
+       "allreduce_overlapped_with_backward": not args.no_overlap, "parameters": nparam, "loss": float(loss.detach()), "config": args.config, "dice_weight": args.dice_weight if BSM else None,
+       "distill_weight": args.distill_weight if DISTILL else None, "distill_mask_dead": bool(args.distill_mask_dead) if DISTILL else None,
+       "distill_frames_warped": int(warped.sum()) if DISTILL else None, "loss_trace": TRACE or None, "graph": bool(args.graph), "graph_replays": graphed.replays if args.graph else 0,
        "update_in_graph": bool(graphed.in_graph_update) if args.graph else None, "optimizer_steps": opt.steps,
        "peak_mem_gb": torch.cuda.max_memory_allocated(dev) / 2**30, "data": "synthetic",
        "fuse_lift_splat": bool(model.backbone.fuse_lift_splat),
