@@ -26,6 +26,16 @@ struct ConvArgs {
 // two more kernel-argument words pushed the 128x128 bf16 kernel (256 VGPRs at two workgroups per CU) into spilling.
 constexpr int kConvModeMask = 0xff, kConvYBf16 = 0x100, kConvResBf16 = 0x200;
 
+// XCD-aware tile walk: workgroup id -> logical tile.  The 8 XCDs (a private 4 MiB L2 each) take consecutive workgroup ids in
+// turn, so XCD x runs the ids x, x + 8, ...; it is given a contiguous run of logical tiles -- the tiles that share a weight or
+// an input panel then meet in one L2.  Bijective for any tile count: with ntiles = 8 q + r the first r XCDs hold q + 1 ids and
+// take runs of q + 1 tiles, the others hold q ids and take runs of q.
+static __device__ __forceinline__ int xcd_tile(int bid, int ntiles) {
+    const int xcd = bid & 7, idx = bid >> 3;
+    const int q = ntiles >> 3, r = ntiles & 7;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
 // Shared by the conv kernel (split_k == 1) and the split-K reduce kernel: scale/shift (folded BN or
 // bias), residual, ReLU, SE gate and the store in the mode's layout.
 static __device__ __forceinline__ void conv_epilogue_store(const ConvArgs &a, int row, int col, float accv) {

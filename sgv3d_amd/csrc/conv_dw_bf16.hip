@@ -110,11 +110,7 @@ __global__ __launch_bounds__(256, (MT == 4 || DEEP) ? 2 : WM == 1 ? (NTAIL ? 3 :
     const int lr = lane & 31, lh = lane >> 5;
 
     // XCD-aware walk: the workgroups that share an XCD's L2 take consecutive logical tiles; the channel tile changes fastest
-    const int ntiles = a.tiles_m * a.tiles_n;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int q = ntiles >> 3, r = ntiles & 7;
-    const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int logical = xcd_tile(blockIdx.x, a.tiles_m * a.tiles_n);
     const int tm = (int)((unsigned)logical / (unsigned)a.tiles_n);
     const int tn = logical - tm * a.tiles_n;
     const int m0 = tm * BM, n0 = tn * BN;
@@ -535,11 +531,7 @@ __global__ __launch_bounds__(256, 3) void conv_dw_bf16_pair_kernel(const DwArgs 
     [[maybe_unused]] const int wm = 0;
     const int wn = __builtin_amdgcn_readfirstlane(wave);
     const int lr = lane & 31, lh = lane >> 5;
-    const int ntiles = a.tiles_m;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int q = ntiles >> 3, r = ntiles & 7;
-    const int tm = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int tm = xcd_tile(blockIdx.x, a.tiles_m);
     [[maybe_unused]] const int n0 = 0;
     const int m0 = tm * BM;
     const __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a.x, 0, (int)a.x_bytes, 0x00020000);

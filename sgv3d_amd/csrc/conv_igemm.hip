@@ -877,6 +877,7 @@ __global__ __launch_bounds__(kThreads, (SPLIT3 && WTM * WTN >= 2) ? 1 : 2) void 
             }                                                                                         \
         }                                                                                             \
     } while (0)
+    // (SPLIT3: the split of f32x3.hpp's split3, with each term stored before the next is formed)
 #define SGV3D_CVT_STORE(DST, V, PLANE)                                                                \
     do {                                                                                              \
         f32x4v f_ = {V.x, V.y, V.z, V.w};                                                             \
@@ -940,7 +941,7 @@ __global__ __launch_bounds__(kThreads, (SPLIT3 && WTM * WTN >= 2) ? 1 : 2) void 
         _Pragma("unroll") for (int nt = 0; nt < WTN; ++nt)                                            \
             acc[mt][nt] = YB ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(fb[PB][nt], fa[PA][mt], acc[mt][nt], 0, 0, 0)     \
                              : __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[PA][mt], fb[PB][nt], acc[mt][nt], 0, 0, 0);
-    // small terms first, so that the leading product meets an accumulator that already holds the corrections
+    // small terms first (the order of f32x3.hpp's x3_term, here on the 32x32x16 instruction with fa / fb as its operands)
 #define SGV3D_MFMA_STEP()                                                                             \
     do {                                                                                              \
         if constexpr (SPLIT3) {                                                                       \

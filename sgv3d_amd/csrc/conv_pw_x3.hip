@@ -6,31 +6,24 @@
 //
 //   y[m][co] = act( scale[co] * sum_ci x[m][ci] * w[co][ci] + shift[co] (+ residual[m][co]) )        m = pixel (NHWC row)
 //
-// Arithmetic: as gemm_x3_grouped.hip -- x = hi + mid + lo exactly (three bf16 terms), the six partial products of weight >=
-// 2^-16 accumulated in f32, the three dropped ones below one f32 rounding of the product.  The WEIGHTS are split once, by the
-// packer (sgv3d_conv_pack_weight_x3: [cout_pad / 16][cin / 32][3][512] bf16, the fragment-ordered layout of the F(4x4) position GEMM's weights).  The
-// ACTIVATIONS stay f32 in HBM (the tensors between the layers do not change) and are split on their way into LDS: a thread
-// loads 4 consecutive channels of a pixel (16 bytes), forms the three bf16 quads (~24 vector instructions, issued in the
-// shadow of the 16-cycle MFMAs of the other waves) and stores three 8-byte pieces.
+// Arithmetic (f32x3.hpp: the split, the six partial products and their order).  The WEIGHTS are split once, by the packer
+// (sgv3d_conv_pack_weight_x3: one weight pack in fragment order, f32x3.hpp).  The ACTIVATIONS stay f32 in HBM (the tensors
+// between the layers do not change) and are split on their way into LDS: a thread loads 4 consecutive channels of a pixel (16
+// bytes), forms the three bf16 quads (~24 vector instructions, issued in the shadow of the 16-cycle MFMAs of the other waves)
+// and stores three 8-byte pieces.
 //
-// Kernel: the core of gemm_x3_grouped_kernel.  Workgroup = WN waves, tile (16 MA) pixels x (32 WN) channels x 32 k; wave w owns
-// channels [32 w, 32 w + 32) and all pixels; C^T = W . X^T so that a lane ends up with 4 consecutive output channels of one
-// pixel (the epilogue is one 16-byte load of scale / shift / residual and one 16-byte store per accumulator tile).  The weights go
-// from global memory straight into the wave's registers (fragment order, nobody else reads a wave's channels); the pixels go
-// through LDS: one image per plane, rows of 64 bytes, 16-byte chunk c of row r at c ^ (-(r >> 2) & 3) (conflict-free fragment
-// reads, see gemm_x3_grouped.hip); one register stage, two LDS buffers, one barrier per k-step.
+// Kernel.  Workgroup = WN waves, tile (16 MA) pixels x (32 WN) channels x 32 k; wave w owns channels [32 w, 32 w + 32) and all
+// pixels; C^T = W . X^T so that a lane ends up with 4 consecutive output channels of one pixel (the epilogue is one 16-byte load of
+// scale / shift / residual and one 16-byte store per accumulator tile).  The k-loop is f32x3.hpp's, with the f32 pixels as its row
+// source in three flavours (pointwise, taps, tap-major: the MODEs below); MODE 3 runs it a second time over its second source.
 //
 // Bound: MFMA bf16 (2.5 PFLOP/s) with 6 x 2 x M x cin x cout executed bf16 flop; HBM for the layers with few input channels.
 #include "conv_common.hpp"
+#include "f32x3.hpp"
 
 using namespace sgv3d;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct PwX3Args {
     const float *x, *scale, *bias, *res;
@@ -72,17 +65,12 @@ template <int MA, int WN, int MODE>
 __global__ __launch_bounds__(64 * WN, 2) void conv_pw_x3_kernel(const PwX3Args a) {
     constexpr bool TAPS = MODE == 1, TM = MODE == 2, DUAL = MODE == 3, DECONV = MODE == 4;
     constexpr int NT = 64 * WN, BM = 16 * MA, BN = 32 * WN;
-    constexpr int PLANE = BM * 64 + 64;
-    constexpr int BUF = 3 * PLANE;
+    constexpr int PLANE = x3_plane_bytes(BM), BUF = x3_buf_bytes(BM);
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * BUF];
 
-    // XCD-aware tile walk (bijective for any tile count); default: the workgroups of one XCD walk the m-tiles of one channel
-    // tile (weight panel shared); mfirst: the channel tiles of one m-tile (pixel rows fetched once)
-    const int ntiles = a.tiles_m * a.tiles_n;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+    // XCD-aware tile walk; default: the workgroups of one XCD walk the m-tiles of one channel tile (weight panel shared);
+    // mfirst: the channel tiles of one m-tile (pixel rows fetched once)
+    const int logical = xcd_tile(blockIdx.x, a.tiles_m * a.tiles_n);
     int tn, tm;
     if (a.mfirst) {
         tm = (int)((unsigned)logical / (unsigned)a.tiles_n);
@@ -154,19 +142,15 @@ __global__ __launch_bounds__(64 * WN, 2) void conv_pw_x3_kernel(const PwX3Args a
     [[maybe_unused]] const int cq = a.cin4;
     [[maybe_unused]] int tm_tap = 0, tm_kh = 0, tm_kw = 0, tm_c4 = 0;
     // LDS: row r, 8-byte piece ach of its 64 bytes: 16-byte chunk (ach >> 1) swizzled, half (ach & 1)
-    const unsigned xl = (unsigned)(arow * 64 + ((((ach >> 1) ^ ((-(arow >> 2)) & 3)) << 4) | ((ach & 1) << 3)));
+    const unsigned xl = (unsigned)(arow * 64 + ((((ach >> 1) ^ x3_swizzle(arow)) << 4) | ((ach & 1) << 3)));
 
-    // ---- weights (U3, fragment order): global -> registers, no LDS (a wave owns its 32 channels)
+    // ---- weights: a wave owns its 32 channels = the channel blocks 2 wave and 2 wave + 1 of the tile
     const int wave = tid >> 6, lane = tid & 63;
     const int l16 = lane & 15, g = lane >> 4;
     unsigned wgo[2];
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
-        const int cb = (n0 >> 4) + 2 * wave + nb;
-        wgo[nb] = (cb * 16 < a.cout_pad) ? (unsigned)(((long long)cb * kb) * 3072 + lane * 16) : 0xffffffffu;
-    }
-    const unsigned sw = (unsigned)((g ^ ((-(l16 >> 2)) & 3)) << 4);
-    const unsigned x_frag = (unsigned)(l16 * 64) + sw;
+    for (int nb = 0; nb < 2; ++nb) wgo[nb] = u3_lane_offset((n0 >> 4) + 2 * wave + nb, kb, lane, a.cout_pad);
+    const unsigned x_frag = X3_FRAG_OFFSET(l16, g);
 
     f32x4 acc[MA][2];
 #pragma unroll
@@ -197,8 +181,8 @@ __global__ __launch_bounds__(64 * WN, 2) void conv_pw_x3_kernel(const PwX3Args a
         tm_kw = tm_tap - tm_kh * a.kw;
     }
 
-    // (TAPS: called with consecutive KT = 0, 1, 2, ...: the tap walk advances by one per call)
-#define PWX3_LOAD_X(KT)                                                                                   \
+    // the k-loop's row source (TAPS: called with consecutive KT = 0, 1, 2, ...: the tap walk advances by one per call)
+#define PWX3_REQUEST(KT)                                                                                  \
     do {                                                                                                  \
         if constexpr (!TAPS && !TM) {                                                                     \
             _Pragma("unroll") for (int i = 0; i < PA; ++i)                                                \
@@ -228,76 +212,19 @@ __global__ __launch_bounds__(64 * WN, 2) void conv_pw_x3_kernel(const PwX3Args a
             }                                                                                             \
         }                                                                                                 \
     } while (0)
-#define PWX3_STORE_X(B)                                                                                   \
+#define PWX3_STORE(B)                                                                                     \
     do {                                                                                                  \
         _Pragma("unroll") for (int i = 0; i < PA; ++i)                                                    \
             if (a_on[i]) {                                                                                \
-                const bf16x4 hi = __builtin_convertvector(rx[i], bf16x4);                                 \
-                const f32x4 r1 = rx[i] - __builtin_convertvector(hi, f32x4);                              \
-                const bf16x4 mid = __builtin_convertvector(r1, bf16x4);                                   \
-                const f32x4 r2 = r1 - __builtin_convertvector(mid, f32x4);                                \
-                const bf16x4 lo = __builtin_convertvector(r2, bf16x4);                                    \
+                bf16x4 hi, mid, lo;                                                                       \
+                split3(rx[i], hi, mid, lo);                                                               \
                 unsigned char *d = smem + (B) * BUF + xl + i * RPA * 64;                                  \
                 *reinterpret_cast<bf16x4 *>(d) = hi;                                                      \
                 *reinterpret_cast<bf16x4 *>(d + PLANE) = mid;                                             \
                 *reinterpret_cast<bf16x4 *>(d + 2 * PLANE) = lo;                                          \
             }                                                                                             \
     } while (0)
-#define PWX3_LOAD_W(KT, ST)                                                                               \
-    do {                                                                                                  \
-        _Pragma("unroll") for (int nb = 0; nb < 2; ++nb)                                                  \
-            _Pragma("unroll") for (int s = 0; s < 3; ++s)                                                 \
-                fw[ST][nb][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, wgo[nb], (kt0 + (KT)) * 3072 + s * 1024, 0)); \
-    } while (0)
-#define PWX3_FRAG(OFF) (*reinterpret_cast<const bf16x8 *>(smem + (OFF)))
-#define PWX3_MFMA(A, B, C) C = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B, C, 0, 0, 0)
-#define PWX3_SB() __builtin_amdgcn_sched_barrier(0)
-    // one k-step (as gemm_x3_grouped.hip): weights of the next k-step requested at the top; the pixels of the next k-step (in
-    // registers since the previous phase) are split and stored to the other LDS buffer behind all but the last block's MFMAs, the
-    // pixels of the k-step after that are requested right behind that store; one barrier per k-step
-#define PWX3_PHASE(KT, B, ST)                                                                             \
-    do {                                                                                                  \
-        if ((KT) + 1 < nkt) PWX3_LOAD_W((KT) + 1, (ST) ^ 1);                                              \
-        bf16x8 fx[2][3];                                                                                  \
-        _Pragma("unroll") for (int s = 0; s < 3; ++s) fx[0][s] = PWX3_FRAG((B) * BUF + x_frag + s * PLANE); \
-        _Pragma("unroll") for (int ma = 0; ma < MA; ++ma) {                                               \
-            if (ma + 1 < MA) {                                                                            \
-                _Pragma("unroll") for (int s = 0; s < 3; ++s)                                             \
-                    fx[(ma + 1) & 1][s] = PWX3_FRAG((B) * BUF + x_frag + (ma + 1) * 16 * 64 + s * PLANE); \
-            }                                                                                             \
-            if (ma == (MA > 2 ? MA - 2 : MA - 1) && (KT) + 1 < nkt) {                                     \
-                PWX3_STORE_X((B) ^ 1);                                                                    \
-                if ((KT) + 2 < nkt) PWX3_LOAD_X((KT) + 2);                                                \
-            }                                                                                             \
-            PWX3_SB();                                                                                    \
-            const bf16x8 *v = fx[ma & 1];                                                                 \
-            _Pragma("unroll") for (int nb = 0; nb < 2; ++nb) {                                            \
-                PWX3_MFMA(fw[ST][nb][2], v[0], acc[ma][nb]);                                              \
-                PWX3_MFMA(fw[ST][nb][0], v[2], acc[ma][nb]);                                              \
-                PWX3_MFMA(fw[ST][nb][1], v[1], acc[ma][nb]);                                              \
-                PWX3_MFMA(fw[ST][nb][1], v[0], acc[ma][nb]);                                              \
-                PWX3_MFMA(fw[ST][nb][0], v[1], acc[ma][nb]);                                              \
-                PWX3_MFMA(fw[ST][nb][0], v[0], acc[ma][nb]);                                              \
-            }                                                                                             \
-            PWX3_SB();                                                                                    \
-        }                                                                                                 \
-        if ((KT) + 1 < nkt) __syncthreads();                                                              \
-    } while (0)
-
-#define PWX3_KLOOP()                                                                                      \
-    do {                                                                                                  \
-        PWX3_LOAD_X(0);                                                                                   \
-        PWX3_LOAD_W(0, 0);                                                                                \
-        PWX3_STORE_X(0);                                                                                  \
-        if (nkt > 1) PWX3_LOAD_X(1);                                                                      \
-        __syncthreads();                                                                                  \
-        int kt = 0;                                                                                       \
-        for (; kt + 1 < nkt; kt += 2) {                                                                   \
-            PWX3_PHASE(kt, 0, 0);                                                                         \
-            PWX3_PHASE(kt + 1, 1, 1);                                                                     \
-        }                                                                                                 \
-        if (kt < nkt) PWX3_PHASE(kt, 0, 0);                                                               \
-    } while (0)
+#define PWX3_KLOOP() X3_KLOOP(MA, smem, w_rsrc, wgo, kt0, nkt, x_frag, fw, acc, PWX3_REQUEST, PWX3_STORE)
 
     PWX3_KLOOP();
     // MODE 3: source A's scaled and shifted sums wait in registers while the same loop runs over source B
@@ -331,21 +258,13 @@ __global__ __launch_bounds__(64 * WN, 2) void conv_pw_x3_kernel(const PwX3Args a
                          : 0xffffffffu;
         }
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-            const int cb = (n0 >> 4) + 2 * wave + nb;
-            wgo[nb] = (cb * 16 < a.cout_pad) ? (unsigned)(((long long)cb * nkt) * 3072 + lane * 16) : 0xffffffffu;
-        }
+        for (int nb = 0; nb < 2; ++nb) wgo[nb] = u3_lane_offset((n0 >> 4) + 2 * wave + nb, nkt, lane, a.cout_pad);
         __syncthreads();                 // (the last k-step's fragment reads of buffer 0 / 1 before the first rows of source B land there)
         PWX3_KLOOP();
     }
 #undef PWX3_KLOOP
-#undef PWX3_LOAD_X
-#undef PWX3_STORE_X
-#undef PWX3_LOAD_W
-#undef PWX3_FRAG
-#undef PWX3_MFMA
-#undef PWX3_SB
-#undef PWX3_PHASE
+#undef PWX3_REQUEST
+#undef PWX3_STORE
 
     // epilogue: accumulator tile (ma, nb) of this lane = pixel m0 + 16 ma + l16, channels n0 + 32 wave + 16 nb + 4 g + (0..3)
     if (a.split_k > 1) {                 // raw partial sums; conv_splitk_reduce4_kernel adds them in fixed order and runs the epilogue
@@ -443,15 +362,9 @@ __global__ __launch_bounds__(256) void pack_weight_x3_kernel(const float *__rest
         ci = k - tap * cin_pad;
     }
     const float v = (co < cout && ci < cin && tap < taps) ? w[((size_t)co * cin + ci) * taps + tap] : 0.f;
-    const __bf16 hi = (__bf16)v;
-    const float r1 = v - (float)hi;
-    const __bf16 mid = (__bf16)r1;
-    const __bf16 lo = (__bf16)(r1 - (float)mid);
-    // fragment order: block of 16 output channels x k-step x plane = 512 elements, (channel c, k) at ((k / 8) * 16 + c) * 8 + k % 8
-    __bf16 *q = u + (((size_t)(co >> 4) * (kp >> 5) + (k >> 5)) * 3) * 512 + ((((k & 31) >> 3) * 16 + (co & 15)) * 8 + (k & 7));
-    q[0] = hi;
-    q[512] = mid;
-    q[1024] = lo;
+    __bf16 hi, mid, lo;
+    split3_rounded(v, hi, mid, lo);
+    u3_store(u3_at(u, co, k, kp), hi, mid, lo);
 }
 
 template <int MA, int WN>

@@ -315,12 +315,7 @@ __global__ __launch_bounds__(256, 1) void conv_wino_kernel(const ConvArgs a) {
     using G = WinoGeom<TC>;
     extern __shared__ __attribute__((aligned(16))) f32x4 smem[];
 
-    // ---- XCD-aware tile mapping (same bijection as the implicit-GEMM kernel) ----------------------
-    const int ntiles = a.tiles_m * a.tiles_n;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int q = ntiles >> 3, r = ntiles & 7;
-    const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int logical = xcd_tile(blockIdx.x, a.tiles_m * a.tiles_n);       // XCD-aware tile walk
     const int tn = logical / a.tiles_m;
     const int tm = logical - tn * a.tiles_m;
     const int bpi = a.wb_y * a.wb_x;
@@ -463,11 +458,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_half_kernel(const ConvArgs a
     extern __shared__ __attribute__((aligned(16))) f32x4 smem[];
 
     // ---- tile mapping: (block of 64 tiles) x (32 output channels); a.tiles_n counts 32-channel tiles here ----
-    const int ntiles = a.tiles_m * a.tiles_n;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int q = ntiles >> 3, r = ntiles & 7;
-    const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+    const int logical = xcd_tile(blockIdx.x, a.tiles_m * a.tiles_n);
     const int tn2 = (int)((unsigned)logical / (unsigned)a.tiles_m);
     const int tm = logical - tn2 * a.tiles_m;
     const int tn = tn2 >> 1, wn = tn2 & 1;          // 64-channel tile of the packed weights, half inside it

@@ -21,6 +21,7 @@
 // decides per layer.  fp32 rounding: the transformed operands are up to 100x the inputs (|B^T| row sums 10), so the error of an
 // output is ~1e-5 of its scale against ~1e-6 for F(2x2); tests/test_conv_wino_gpu.py bounds it against float64.
 #include "conv_common.hpp"
+#include "f32x3.hpp"
 
 using namespace sgv3d;
 
@@ -320,18 +321,9 @@ __global__ __launch_bounds__(256) void wino4_pack_weight_kernel(const float *__r
     }
 }
 
-// ---- f32x3 forms (gemm_x3_grouped.hip): the operands of the position GEMMs as three bf16 planes ---------------------------
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-
-// x = hi + mid + lo exactly (8 + 8 + 8 significand bits; the remainders x - hi and x - hi - mid are exact in f32)
+// ---- f32x3 forms (f32x3.hpp): the operands of the position GEMMs as three bf16 planes -------------------------------------
 __device__ __forceinline__ void split3(const f4 &x, bf16x4 &hi, bf16x4 &mid, bf16x4 &lo) {
-    const f32x4v v = {x.x, x.y, x.z, x.w};
-    hi = __builtin_convertvector(v, bf16x4);
-    const f32x4v r1 = v - __builtin_convertvector(hi, f32x4v);
-    mid = __builtin_convertvector(r1, bf16x4);
-    const f32x4v r2 = r1 - __builtin_convertvector(mid, f32x4v);
-    lo = __builtin_convertvector(r2, bf16x4);
+    sgv3d::split3(f32x4{x.x, x.y, x.z, x.w}, hi, mid, lo);
 }
 
 // as wino4_input_kernel, writing V3 [36][rows][cin/32][3][32] bf16: one thread = one tile x 4 input channels -> three 8-byte
@@ -385,17 +377,6 @@ __global__ __launch_bounds__(kTB) void wino4_input_x3_multi_kernel(const Wino4Mu
     wino4_input_x3_body<true>(m.a[l], (long long)((int)blockIdx.x - m.first[l]) * kTB + threadIdx.x);
 }
 
-// The three bf16 terms of the f32 number v, contraction off: where v is a product, v - hi would otherwise fuse with the
-// multiplication into one multiply-add and mid would carry the product's UNROUNDED tail (576 * (1 / 6) came out as
-// 96 + 2.9e-6) -- the f32x3 weights are to be the terms of the rounded f32 weight, integer where that is.
-__device__ __forceinline__ void split3_rounded(float v, __bf16 &hi, __bf16 &mid, __bf16 &lo) {
-#pragma clang fp contract(off)
-    hi = (__bf16)v;
-    const float r1 = v - (float)hi;
-    mid = (__bf16)r1;
-    lo = (__bf16)(r1 - (float)mid);
-}
-
 // U3[p][co / 16][ci / 32][plane][fragment order] = the three bf16 terms of (G g G^T)[i][j], p = 6 i + j; zero rows / columns in the padding.
 // One thread per (co, ci); the arithmetic of wino4_pack_weight_kernel, then the split.
 __global__ __launch_bounds__(256) void wino4_pack_weight_x3_kernel(const float *__restrict__ w, int cout, int cin, int k_pad,
@@ -423,9 +404,7 @@ __global__ __launch_bounds__(256) void wino4_pack_weight_x3_kernel(const float *
         t[5][b] = g[2][b];
     }
     const size_t block = (size_t)cout_pad * k_pad * 3;
-    // fragment order (gemm_x3_grouped.hip): block of 16 output channels x k-step x plane = 512 elements, (channel c, k) at
-    // ((k / 8) * 16 + c) * 8 + k % 8
-    __bf16 *ub = u + (((size_t)(co >> 4) * (k_pad >> 5) + (ci >> 5)) * 3) * 512 + ((((ci & 31) >> 3) * 16 + (co & 15)) * 8 + (ci & 7));
+    __bf16 *ub = u3_at(u, co, ci, k_pad);
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
         const float s02 = t[r][0] + t[r][2];
@@ -436,10 +415,7 @@ __global__ __launch_bounds__(256) void wino4_pack_weight_x3_kernel(const float *
         for (int c = 0; c < 6; ++c) {
             __bf16 hi, mid, lo;
             split3_rounded(o[c], hi, mid, lo);
-            __bf16 *q = ub + (size_t)(r * 6 + c) * block;
-            q[0] = hi;
-            q[512] = mid;
-            q[1024] = lo;
+            u3_store(ub + (size_t)(r * 6 + c) * block, hi, mid, lo);
         }
     }
 }

@@ -51,11 +51,7 @@ __global__ __launch_bounds__(kThreads, 3) void dcn3x3_fused_kernel(const DcnArgs
     float *const Xs0 = smem;
     float *const Ws0 = smem + BM * BK;
 
-    const int ntiles = a.tiles_m * a.tiles_ng;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+    const int logical = xcd_tile(blockIdx.x, a.tiles_m * a.tiles_ng);
     const int tng = (int)((unsigned)logical / (unsigned)a.tiles_m);      // (group, n-tile): changes slowest -> shared weight panel
     const int tm = logical - tng * a.tiles_m;
     const int tn_per_g = a.tiles_ng / a.groups;

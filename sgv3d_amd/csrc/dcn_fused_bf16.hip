@@ -108,11 +108,7 @@ __global__ __launch_bounds__(kThreads, 2) void dcn3x3_fused_bf16_kernel(const Dc
     // XCD-aware walk (as dcn3x3_fused_kernel): the workgroups of one XCD take consecutive logical tiles; the pixel tile changes
     // fastest, so that an XCD's L2 holds one group's weights and a band of the input map
     const int per_m = a.groups * a.nchunk;
-    const int ntiles = a.tiles_m * per_m;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+    const int logical = xcd_tile(blockIdx.x, a.tiles_m * per_m);
     const int tgc = (int)((unsigned)logical / (unsigned)a.tiles_m);      // (group, channel chunk)
     const int tm = logical - tgc * a.tiles_m;
     const int grp = tgc / a.nchunk;

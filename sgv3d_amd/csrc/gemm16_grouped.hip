@@ -54,12 +54,8 @@ __global__ __launch_bounds__(kThreads, 5) void gemm16_grouped_kernel(const G16Ar
     float *const Xs0 = smem;
     float *const Ws0 = smem + BM * BK;
 
-    // XCD-aware tile mapping (bijective for any tile count): the workgroups of one XCD walk consecutive m-tiles of one n-tile
-    const int ntiles = a.tiles_m * a.tiles_n;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+    // XCD-aware tile walk: the workgroups of one XCD walk consecutive m-tiles of one n-tile
+    const int logical = xcd_tile(blockIdx.x, a.tiles_m * a.tiles_n);
     const int tn = (int)((unsigned)logical / (unsigned)a.tiles_m);
     const int tm = logical - tn * a.tiles_m;
     const int m0 = tm * BM, n0 = tn * BN;

@@ -5,21 +5,15 @@
 //
 //   M[p][t][co] = sum_ci V[p][t][ci] * U[p][co][ci]        p = 0..35 positions, t = Winograd tiles (rows)
 //
-// Arithmetic.  Every f32 operand x is split EXACTLY into three bf16 terms, hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi -
-// mid) (the remainders are exact in f32: 3 x 8 significand bits = f32's 24), by the kernels that PRODUCE the operands -- the
-// weight packer once per parameter version, the input transform (a bandwidth-bound kernel) per call -- so this kernel holds no
-// conversion instruction.  A product v * u is the f32 sum of the six partial products of weight >= 2^-16,
-//   lo_u hi_v + hi_u lo_v + mid_u mid_v + mid_u hi_v + hi_u mid_v + hi_u hi_v,
-// accumulated in f32 by the MFMA; the three dropped ones are below 2^-24 of the product: one f32 rounding, as
-// v_mfma_f32_16x16x4_f32 would commit.  Six v_mfma_f32_16x16x32_bf16 (16 cycles each, K = 32) do the work of eight
-// v_mfma_f32_16x16x4_f32 (32 cycles each): 96 cycles against 256.
+// Arithmetic (f32x3.hpp: the split, the six partial products and their order).  The operands are split by the kernels that
+// PRODUCE them -- the weight packer once per parameter version, the input transform (a bandwidth-bound kernel) per call -- so this
+// kernel holds no conversion instruction.
 //
-// Layouts (bf16, "plane-interleaved k-chunks"): a row of an operand is K / 32 records of 192 bytes, record = [hi | mid | lo] x 32
+// Layouts (bf16, "plane-interleaved k-chunks"): a row of V3 is K / 32 records of 192 bytes, record = [hi | mid | lo] x 32
 // consecutive k.  One k-step of a row is one contiguous 192-byte read.
 //   V3  [36][rows][K/32][3][32]      written by wino4_input_x3_kernel        rows = tiles padded to the m-tile (16 MA)
-//   U3  [36][cout_pad/16][K/32][3][512]  written by wino4_pack_weight_x3_kernel, FRAGMENT order: block of 16 output channels x
-//       k-step x plane = 1024 contiguous bytes, element (channel c, k) at ((k / 8) * 16 + c) * 8 + k % 8 -- the 64 lanes of a
-//       wave load one MFMA operand with one buffer_load_dwordx4 each, contiguously; cout_pad = cout rounded up to 32
+//   U3  [36][cout_pad/16][K/32][3][512]  written by wino4_pack_weight_x3_kernel: 36 weight packs in fragment order (f32x3.hpp);
+//       cout_pad = cout rounded up to 32
 //   M   [36][rows][N] f32            read by wino4_output_kernel (unchanged)
 //
 // Kernel.  Workgroup = WN waves; tile (16 MA) rows x (32 WN) columns x 32 k; wave w owns columns [32 w, 32 w + 32) and all rows:
@@ -27,14 +21,9 @@
 // with 4 consecutive output channels of one row: one 16-byte store per accumulator tile.  Per k-step a wave reads 6 weight
 // fragments once and 3 row fragments per row block (ds_read_b128 each) for 12 MA MFMAs: (3 MA + 6) / (12 MA) reads per MFMA --
 // 0.32 at MA = 7, a third of what saturates the LDS array beside 16-cycle MFMAs.
-//   weights  never touch LDS: a wave's 6 fragments of a k-step (2 column blocks x 3 planes, 1 KB each) come from L2 straight into
-//            registers with one buffer_load_dwordx4 per lane and fragment, requested one k-step ahead.
-//   LDS      the ROW tile only, two buffers of three planes; rows of 64 bytes (32 k), the 16-byte chunk c of row r stored at
-//            c ^ (-(r >> 2) & 3): the four 16-lane groups of a ds_read_b128 (rows {0-3, 12-15} at one chunk with rows {4-11} at the
-//            next, and so on) each fall on 64 distinct banks; a plane is BM x 64 + 64 bytes so that the 8-lane groups of a staging
-//            store that straddle two planes or two rows use both halves of the banks.  2 x 3 x (16 MA x 64 + 64) B: 43 KB at MA 7.
-//   pipeline the rows of k-step k + 1 are in registers while k-step k computes, stored into the OTHER buffer behind its MFMAs: ONE
-//            barrier per k-step.  Two workgroups per CU (launch bound), sched_barriers keep the request / MFMA / store order.
+//   k-loop   f32x3.hpp's (weights from L2 straight into registers, the row tile through two swizzled LDS buffers, one barrier per
+//            k-step), with the pre-split rows as its row source: three 16-byte loads and stores per lane and pass, no arithmetic.
+//            2 x 3 x (16 MA x 64 + 64) B of LDS: 43 KB at MA 7.  Two workgroups per CU (launch bound).
 //            (Prefetch distance 2, three workgroups per CU, 64-thread workgroups: measured, no gain -- DESIGN 3.9.)
 //   traffic  a k-step loads 16 MA x 192 B of rows per workgroup and 32 WN x 192 B of weights (registers) for 12 MA x WN x 8192 MACs:
 //            10 MACs per byte at MA 7, WN 4 -- 1.5 x the bytes of the f32 kernel for 2.7 x its MFMA rate.
@@ -43,14 +32,11 @@
 //
 // Bound: MFMA bf16 (2.5 PFLOP/s) with executed work 6 x 2 x 36 x rows x cin x cout bf16 flop per launch.
 #include "conv_common.hpp"
+#include "f32x3.hpp"
 
 using namespace sgv3d;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct GX3Args {
     const void *x, *w;     // V3, U3
@@ -66,17 +52,12 @@ struct GX3Args {
 template <int MA, int WN>
 __global__ __launch_bounds__(64 * WN, 2) void gemm_x3_grouped_kernel(const GX3Args a) {
     constexpr int NT = 64 * WN, BM = 16 * MA, BN = 32 * WN;
-    constexpr int PLANE = BM * 64 + 64;            // one plane of the row tile; + 64: see the header
-    constexpr int BUF = 3 * PLANE;
+    constexpr int PLANE = x3_plane_bytes(BM), BUF = x3_buf_bytes(BM);
     __shared__ __attribute__((aligned(16))) unsigned char smem[2 * BUF];
 
-    // XCD-aware tile mapping (bijective for any tile count)
+    // XCD-aware tile walk: m fastest, then n, then position
     const int per_pos = a.tiles_m * a.tiles_n;
-    const int ntiles = 36 * per_pos;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, idx = bid >> 3;
-    const int q8 = ntiles >> 3, r8 = ntiles & 7;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+    const int logical = xcd_tile(blockIdx.x, 36 * per_pos);
     const int p = (int)((unsigned)logical / (unsigned)per_pos);
     const int rem = logical - p * per_pos;
     const int tn = (int)((unsigned)rem / (unsigned)a.tiles_m);
@@ -89,31 +70,39 @@ __global__ __launch_bounds__(64 * WN, 2) void gemm_x3_grouped_kernel(const GX3Ar
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<unsigned char *>(static_cast<const unsigned char *>(a.w)) + (size_t)p * a.w_stride, 0, (int)a.w_bytes, 0x00020000);
 
-    // ---- rows (V3): global -> registers -> LDS.  A pass moves one PLANE of NT / 4 rows: lane (tid >> 2, tid & 3) the 16-byte chunk
-    // tid & 3 of row (tid >> 2) + RP pass.  One per-thread base; pass / plane / k-step go into the load's scalar offset and the
-    // store's immediate (the swizzle key (row >> 2) & 3 does not depend on the pass: RP % 16 == 0).
+    // ---- rows (V3, split by their producer): global -> registers -> LDS.  A pass moves one PLANE of NT / 4 rows: lane
+    // (tid >> 2, tid & 3) the 16-byte chunk tid & 3 of row (tid >> 2) + RP pass.  One per-thread base; pass / plane / k-step go into
+    // the load's scalar offset and the store's immediate (the swizzle key of a row does not depend on the pass: RP % 16 == 0).
     constexpr int RP = NT / 4, PA = (BM + RP - 1) / RP;
     static_assert(RP % 16 == 0, "a pass is a multiple of 16 rows");
     const int srow = tid >> 2, sch = tid & 3;
     const unsigned row_b = (unsigned)kb * 192u;                                   // bytes per row
     const unsigned xg = (unsigned)((long long)(m0 + srow) * kb * 192 + sch * 16);
-    const unsigned sl = (unsigned)(srow * 64 + ((sch ^ ((-(srow >> 2)) & 3)) << 4));
+    const unsigned sl = (unsigned)(srow * 64 + ((sch ^ x3_swizzle(srow)) << 4));
     bool a_on[PA];
 #pragma unroll
     for (int i = 0; i < PA; ++i) a_on[i] = (srow & ~15) + RP * i < BM;           // wave-uniform: a wave covers 16 rows
+#define GX3_REQUEST(KT)                                                                                   \
+    do {                                                                                                  \
+        _Pragma("unroll") for (int s = 0; s < 3; ++s)                                                     \
+            _Pragma("unroll") for (int i = 0; i < PA; ++i)                                                \
+                rx[s][i] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(                \
+                    x_rsrc, a_on[i] ? xg : 0xffffffffu, (int)(row_b * (unsigned)(RP * i)) + (KT) * 192 + s * 64, 0)); \
+    } while (0)
+#define GX3_STORE(B)                                                                                      \
+    do {                                                                                                  \
+        _Pragma("unroll") for (int s = 0; s < 3; ++s)                                                     \
+            _Pragma("unroll") for (int i = 0; i < PA; ++i)                                                \
+                if (a_on[i]) *reinterpret_cast<i32x4 *>(smem + (B) * BUF + sl + s * PLANE + i * RP * 64) = rx[s][i]; \
+    } while (0)
 
-    // ---- weights (U3, fragment order): global -> registers, no LDS -- a wave owns its 32 columns, nobody else reads them.
-    // Block cb = 16 output channels; (cb, k-step, plane) = 1024 contiguous bytes, lane l at 16 l.
+    // ---- weights: a wave owns its 32 columns = the channel blocks 2 wave and 2 wave + 1 of the tile
     const int wave = tid >> 6, lane = tid & 63;
     const int l16 = lane & 15, g = lane >> 4;
     unsigned wgo[2];
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
-        const int cb = (n0 >> 4) + 2 * wave + nb;
-        wgo[nb] = (cb * 16 < a.cout_pad) ? (unsigned)(((long long)cb * kb) * 3072 + lane * 16) : 0xffffffffu;
-    }
-    const unsigned sw = (unsigned)((g ^ ((-(l16 >> 2)) & 3)) << 4);
-    const unsigned x_frag = (unsigned)(l16 * 64) + sw;                               // + 16 ma rows, + plane, + buffer
+    for (int nb = 0; nb < 2; ++nb) wgo[nb] = u3_lane_offset((n0 >> 4) + 2 * wave + nb, kb, lane, a.cout_pad);
+    const unsigned x_frag = X3_FRAG_OFFSET(l16, g);
 
     f32x4 acc[MA][2];
 #pragma unroll
@@ -121,83 +110,11 @@ __global__ __launch_bounds__(64 * WN, 2) void gemm_x3_grouped_kernel(const GX3Ar
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) acc[ma][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    i32x4 rx[3][PA];
-    bf16x8 fw[2][2][3];                             // [stage][nb][plane]
-    const int nkt = kb;
-
-#define GX3_LOAD_X(KT)                                                                                    \
-    do {                                                                                                  \
-        _Pragma("unroll") for (int s = 0; s < 3; ++s)                                                     \
-            _Pragma("unroll") for (int i = 0; i < PA; ++i)                                                \
-                rx[s][i] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(                \
-                    x_rsrc, a_on[i] ? xg : 0xffffffffu, (int)(row_b * (unsigned)(RP * i)) + (KT) * 192 + s * 64, 0)); \
-    } while (0)
-#define GX3_STORE_X(B)                                                                                    \
-    do {                                                                                                  \
-        _Pragma("unroll") for (int s = 0; s < 3; ++s)                                                     \
-            _Pragma("unroll") for (int i = 0; i < PA; ++i)                                                \
-                if (a_on[i]) *reinterpret_cast<i32x4 *>(smem + (B) * BUF + sl + s * PLANE + i * RP * 64) = rx[s][i]; \
-    } while (0)
-#define GX3_LOAD_W(KT, ST)                                                                                \
-    do {                                                                                                  \
-        _Pragma("unroll") for (int nb = 0; nb < 2; ++nb)                                                  \
-            _Pragma("unroll") for (int s = 0; s < 3; ++s)                                                 \
-                fw[ST][nb][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, wgo[nb], (KT) * 3072 + s * 1024, 0)); \
-    } while (0)
-#define GX3_FRAG(OFF) (*reinterpret_cast<const bf16x8 *>(smem + (OFF)))
-#define GX3_MFMA(A, B, C) C = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A, B, C, 0, 0, 0)
-#define GX3_SB() __builtin_amdgcn_sched_barrier(0)
-    // One k-step: MFMAs from LDS buffer B and weight stage ST.  The weights of the next k-step are requested at the top; the rows of
-    // the next k-step (in registers since the previous phase) go to the other LDS buffer behind all but the last block's MFMAs, the
-    // rows of the k-step after that are requested right behind that store; one barrier per k-step.
-#define GX3_PHASE(KT, B, ST)                                                                              \
-    do {                                                                                                  \
-        if ((KT) + 1 < nkt) GX3_LOAD_W((KT) + 1, (ST) ^ 1);                                               \
-        bf16x8 fx[2][3];                                                                                  \
-        _Pragma("unroll") for (int s = 0; s < 3; ++s) fx[0][s] = GX3_FRAG((B) * BUF + x_frag + s * PLANE); \
-        _Pragma("unroll") for (int ma = 0; ma < MA; ++ma) {                                               \
-            if (ma + 1 < MA) {                                                                            \
-                _Pragma("unroll") for (int s = 0; s < 3; ++s)                                             \
-                    fx[(ma + 1) & 1][s] = GX3_FRAG((B) * BUF + x_frag + (ma + 1) * 16 * 64 + s * PLANE);  \
-            }                                                                                             \
-            if (ma == (MA > 2 ? MA - 2 : MA - 1) && (KT) + 1 < nkt) {                                     \
-                GX3_STORE_X((B) ^ 1);                                                                     \
-                if ((KT) + 2 < nkt) GX3_LOAD_X((KT) + 2);                                                 \
-            }                                                                                             \
-            GX3_SB();                                                                                     \
-            const bf16x8 *v = fx[ma & 1];                                                                 \
-            _Pragma("unroll") for (int nb = 0; nb < 2; ++nb) {                                            \
-                /* small terms first: (u lo, v hi), (u hi, v lo), (mid, mid), (u mid, v hi), (u hi, v mid), (hi, hi) */ \
-                GX3_MFMA(fw[ST][nb][2], v[0], acc[ma][nb]);                                               \
-                GX3_MFMA(fw[ST][nb][0], v[2], acc[ma][nb]);                                               \
-                GX3_MFMA(fw[ST][nb][1], v[1], acc[ma][nb]);                                               \
-                GX3_MFMA(fw[ST][nb][1], v[0], acc[ma][nb]);                                               \
-                GX3_MFMA(fw[ST][nb][0], v[1], acc[ma][nb]);                                               \
-                GX3_MFMA(fw[ST][nb][0], v[0], acc[ma][nb]);                                               \
-            }                                                                                             \
-            GX3_SB();                                                                                     \
-        }                                                                                                 \
-        if ((KT) + 1 < nkt) __syncthreads();                                                              \
-    } while (0)
-
-    GX3_LOAD_X(0);
-    GX3_LOAD_W(0, 0);
-    GX3_STORE_X(0);
-    if (nkt > 1) GX3_LOAD_X(1);
-    __syncthreads();
-    int kt = 0;
-    for (; kt + 1 < nkt; kt += 2) {
-        GX3_PHASE(kt, 0, 0);
-        GX3_PHASE(kt + 1, 1, 1);
-    }
-    if (kt < nkt) GX3_PHASE(kt, 0, 0);
-#undef GX3_LOAD_X
-#undef GX3_STORE_X
-#undef GX3_LOAD_W
-#undef GX3_FRAG
-#undef GX3_MFMA
-#undef GX3_SB
-#undef GX3_PHASE
+    i32x4 rx[3][PA];                                // the row source's registers
+    bf16x8 fw[2][2][3];
+    X3_KLOOP(MA, smem, w_rsrc, wgo, 0, kb, x_frag, fw, acc, GX3_REQUEST, GX3_STORE);
+#undef GX3_REQUEST
+#undef GX3_STORE
 
     // accumulator tile (ma, nb): row (Winograd tile) m0 + 16 ma + l16, columns n0 + 32 wave + 16 nb + 4 g + (0..3)
 #pragma unroll

@@ -1,6 +1,6 @@
 // The image stem in one launch: NCHW image -> 7x7 / stride 2 / pad 3 convolution (3 -> 64) + folded BN + ReLU -> 3x3 / stride 2 / pad 1
 // max-pool -> NHWC map (mmdet ResNet's conv1 / bn1 / relu / maxpool, built at layers/backbones/lss_fpn.py:296-297), with
-// float32-accurate products on the bf16 matrix cores ("f32x3", as conv_pw_x3.hip).  It replaces three launches -- nchw_to_nhwc_kernel
+// float32-accurate products on the bf16 matrix cores ("f32x3", f32x3.hpp).  It replaces three launches -- nchw_to_nhwc_kernel
 // (c_pad 4), the tap-major stem convolution and maxpool3x3s2_kernel -- and the two maps between them (the 4-channel NHWC copy of
 // the image and the un-pooled 64-channel map, written and read once each) never reach memory.
 //
@@ -11,11 +11,10 @@
 // maxpool3x3s2_kernel.  The weights are that launch's pack, unchanged (sgv3d_conv_pack_weight_x3, k order 0: k = tap * 4 + ci, K = 196
 // padded to 224 = 7 k-steps of 8 taps x 4 channels, fragment order).  A pixel fragment holds for lane (l16, g) of k-step kt the k range
 // [32 kt + 8 g, 32 kt + 8 g + 8) = taps 8 kt + 2 g and 8 kt + 2 g + 1 x 4 channels of conv pixel l16, what that kernel's LDS rows hold;
-// channel 3, the taps outside the image and taps >= 49 are zeros, as its masked loads return; a value is split by the same three
-// conversions; the six partial products of a k-step are issued in gemm_x3_grouped.hip's order on a zeroed accumulator, the k-steps in
-// order; the epilogue is the same fused multiply-add and fmaxf.  An MFMA's result for one (channel, pixel) element depends on that
-// element's operands only, so which 16 pixels share an instruction does not matter.  max is exact; the pool uses maxpool3x3s2_kernel's
-// NaN-propagating comparison in its window order.
+// channel 3, the taps outside the image and taps >= 49 are zeros, as its masked loads return; the split and the order of a k-step's
+// six partial products are f32x3.hpp's, on a zeroed accumulator, the k-steps in order; the epilogue is the same fused multiply-add and
+// fmaxf.  An MFMA's result for one (channel, pixel) element depends on that element's operands only, so which 16 pixels share an
+// instruction does not matter.  max is exact; the pool uses maxpool3x3s2_kernel's NaN-propagating comparison in its window order.
 //
 // Kernel.  A tile is TPH x TPW = 4 x 16 pooled pixels of one image: 9 x 33 conv pixels from a 23 x 71 input patch.  One persistent
 // workgroup of 4 waves per CU walks the tiles w, w + gridDim.x, ...: its weights stay in registers over all of them, and the patch of
@@ -37,14 +36,11 @@
 //
 // Bound: MFMA bf16 with 6 x 2 x (20 x 16 pixels per tile) x 64 x 224 executed flop; HBM traffic is the image once and the pooled map once.
 #include "conv_common.hpp"
+#include "f32x3.hpp"
 
 using namespace sgv3d;
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 struct StemPoolArgs {
     const float *x, *scale, *shift;
@@ -84,8 +80,7 @@ __global__ __launch_bounds__(256) void stem_pool_x3_kernel(const StemPoolArgs a)
         for (int kt = 0; kt < KT; ++kt)
 #pragma unroll
             for (int s = 0; s < 3; ++s)
-                fw[nb][kt][s] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
-                                                               w_rsrc, (unsigned)(lane * 16 + half * (2 * KT * 3072)), (nb * KT + kt) * 3072 + s * 1024, 0));
+                fw[nb][kt][s] = u3_load(w_rsrc, u3_lane_offset(2 * half, KT, lane), nb * KT + kt, s);
 
     // ---- patch: NCHW planes -> registers (requested one tile ahead) -> three bf16 planes of 4-channel pixels in LDS; zeros outside
     // the image (the load's offset is then out of the buffer's range and returns 0) and in channel 3
@@ -150,11 +145,8 @@ __global__ __launch_bounds__(256) void stem_pool_x3_kernel(const StemPoolArgs a)
             const int idx = tid + 256 * i;
             if (idx >= NPATCH) continue;
             const f32x4 x4 = {v[i][0], v[i][1], v[i][2], 0.f};
-            const bf16x4 hi = __builtin_convertvector(x4, bf16x4);
-            const f32x4 r1 = x4 - __builtin_convertvector(hi, f32x4);
-            const bf16x4 mid = __builtin_convertvector(r1, bf16x4);
-            const f32x4 r2 = r1 - __builtin_convertvector(mid, f32x4);
-            const bf16x4 lo = __builtin_convertvector(r2, bf16x4);
+            bf16x4 hi, mid, lo;
+            split3(x4, hi, mid, lo);
             unsigned char *d = smem + idx * 8;
             *reinterpret_cast<bf16x4 *>(d) = hi;
             *reinterpret_cast<bf16x4 *>(d + PLANE) = mid;
@@ -194,24 +186,20 @@ __global__ __launch_bounds__(256) void stem_pool_x3_kernel(const StemPoolArgs a)
         }                                                                                                          \
         fx[D][u][s] = __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);                                     \
     }
-#define STEM_MFMA(WS, XS)                                                                                          \
-    _Pragma("unroll") for (int u = 0; u < 2; ++u) _Pragma("unroll") for (int nb = 0; nb < 2; ++nb)                 \
-        acc[u][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[nb][kt][WS], fx[kt & 1][u][XS], acc[u][nb], 0, 0, 0)
             STEM_LOAD_FX(0, 0)
 #pragma unroll
             for (int kt = 0; kt < KT; ++kt) {
                 if (kt + 1 < KT) STEM_LOAD_FX(kt + 1, (kt + 1) & 1)
                 __builtin_amdgcn_sched_barrier(0);
-                // small terms first: (w lo, x hi), (w hi, x lo), (mid, mid), (w mid, x hi), (w hi, x mid), (hi, hi)
-                STEM_MFMA(2, 0);
-                STEM_MFMA(0, 2);
-                STEM_MFMA(1, 1);
-                STEM_MFMA(1, 0);
-                STEM_MFMA(0, 1);
-                STEM_MFMA(0, 0);
+                // the four accumulator chains take their six terms in turn
+#pragma unroll
+                for (int t = 0; t < 6; ++t)
+#pragma unroll
+                    for (int u = 0; u < 2; ++u)
+#pragma unroll
+                        for (int nb = 0; nb < 2; ++nb) x3_term(t, fw[nb][kt], fx[kt & 1][u], acc[u][nb]);
                 __builtin_amdgcn_sched_barrier(0);
             }
-#undef STEM_MFMA
 #undef STEM_LOAD_FX
             // accumulator (u, nb) of this lane = conv pixel p[u], channels 32 half + 16 nb + 4 g + (0..3)
 #pragma unroll
