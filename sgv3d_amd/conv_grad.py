@@ -339,7 +339,9 @@ def conv2d_backward_data(dy, weight, in_hw, stride=1, pad=0, dil=1, add_to=None)
     assert kh == kw, "square kernels only (every layer of the model)"
     if dy.dtype == torch.bfloat16:
         # bf16 activation storage: the gradient maps stay bf16 (PackedConv's io bits); 16-byte pixel rows on both sides
-        assert cin % 8 == 0 and int(dy.shape[-1]) % 8 == 0 and not (kh == stride and stride > 1), "bf16 data gradient: channel counts % 8, no patchify layers"
+        # (patchify: the transposed-convolution branch below -- kernel == stride WITH padding or dilation is an ordinary strided layer)
+        assert cin % 8 == 0 and int(dy.shape[-1]) % 8 == 0 and not (kh == stride and stride > 1 and pad == 0 and dil == 1), \
+            "bf16 data gradient: channel counts % 8, no patchify layers"
         okw = dict(out_dtype=torch.bfloat16)
     else:
         okw = {}
@@ -353,6 +355,11 @@ def conv2d_backward_data(dy, weight, in_hw, stride=1, pad=0, dil=1, add_to=None)
         ph, pw = H - int(dx.shape[1]), W - int(dx.shape[2])
         return dx if ph == 0 and pw == 0 else torch.nn.functional.pad(dx, (0, 0, 0, pw, 0, ph))   # rows the conv never read
     cp, rpad = int(dy.shape[-1]), dil * (kh - 1) - pad
+    if rpad < 0 and not (stride == 2 and dil == 1):
+        # (the four-phase form of stride 2 pads each phase by what it needs; every other form runs the rotated layer at ``rpad``, which
+        # no launcher takes negative: refused here, before a weight is packed or a candidate timed)
+        raise _lib.SGV3DError(f"conv2d_backward_data: the {cout}x{cin} k{kh}x{kw} s{stride} p{pad} d{dil} layer pads by more than its kernel "
+                              f"reaches (pad {pad} > dil * (k - 1) = {dil * (kh - 1)}): its data gradient would be a convolution with padding {rpad}")
     # the stride-1 convolution with the weights rotated by 180 degrees and in / out swapped ([cin, cout, kh, kw])
     make = lambda w: PackedConv(_rot180_transpose(w), stride=1, pad=rpad, dil=dil, cin_pad=cp, pad_out=True)
     conv = lambda x, **kw: _packed_call(weight, ('dgrad', rpad, dil, cp), make, x, **okw, **kw)
