@@ -2091,15 +2091,32 @@ def centerhead_branches_f4(x, u, scale1, shift1, w2, b2, out_begin, num_branches
     return out
 
 
+HEAD_BF16_MAX_OUT = 4           # columns head_bf16_pack_w2_kernel keeps per branch (csrc/head_bf16.hip)
+HEAD_BF16_MAX_BRANCHES = 48     # kMaxBranches of csrc/head_bf16.hip
+
+
 def pack_centerhead_bf16(w1, w2, out_begin):
     """First layers of the CenterHead branches concatenated, f32 [nb*64, 64, 3, 3], and final layers f32 [sum_c, 3, 3, 64]
     with ``out_begin`` int32 [nb+1] -> the two bf16 buffers sgv3d_centerhead_branches_forward_bf16 streams
-    (fragment-ordered first layers; [branch][tap][4][64] final layers)."""
+    (fragment-ordered first layers; [branch][tap][4][64] final layers).
+    The kernel computes at most HEAD_BF16_MAX_OUT = 4 outputs per branch and at most HEAD_BF16_MAX_BRANCHES = 48 branches.  The
+    packer keeps columns 0..3 of a branch only and the kernel would store a copy of them into the planes of a wider one, and the
+    C entry cannot see the table (device memory), so the table is read back and checked HERE, once per weight load:
+    ``out_begin`` starts at 0, does not decrease, ends at sum_c, and no branch is wider than 4; else ValueError, before any
+    launch.  (A zero-width branch is fine: it has first-layer weights and no outputs.)"""
     w1 = w1.detach().float().contiguous()
     w2 = w2.detach().float().contiguous()
     nb = int(w1.shape[0]) // 64
     assert int(w1.shape[0]) == nb * 64 and tuple(w1.shape[1:]) == (64, 3, 3), "bf16 fused head: 64 -> 64 3x3 first layers"
     assert tuple(w2.shape[1:]) == (3, 3, 64) and int(out_begin.numel()) == nb + 1 and out_begin.dtype == torch.int32
+    ob = [int(v) for v in out_begin.tolist()]
+    widths = [b - a for a, b in zip(ob, ob[1:])]
+    if nb < 1 or nb > HEAD_BF16_MAX_BRANCHES:
+        raise ValueError(f"bf16 fused head: 1..{HEAD_BF16_MAX_BRANCHES} branches, got {nb}")
+    if ob[0] != 0 or ob[-1] != int(w2.shape[0]) or any(c < 0 for c in widths):
+        raise ValueError(f"bf16 fused head: out_begin must start at 0, not decrease and end at {int(w2.shape[0])} (the rows of w2), got {ob}")
+    if any(c > HEAD_BF16_MAX_OUT for c in widths):
+        raise ValueError(f"bf16 fused head: a branch has at most {HEAD_BF16_MAX_OUT} outputs, got widths {widths}")
     lib = _lib.load()
     p1 = torch.empty(lib.sgv3d_centerhead_bf16_weight_bytes(nb), dtype=torch.uint8, device=w1.device)
     p2 = torch.empty(lib.sgv3d_centerhead_bf16_weight2_bytes(nb), dtype=torch.uint8, device=w1.device)
@@ -2113,8 +2130,11 @@ def pack_centerhead_bf16(w1, w2, out_begin):
 
 
 def centerhead_branches_bf16(x, packed, scale1, shift1, b2, out_begin, num_branches, out=None, x_coff=0):
-    """bf16-MFMA version of ``centerhead_branches``: x NHWC f32 [B,H,W,ld] (channels [x_coff, x_coff+64)), ``packed`` from
-    ``pack_centerhead_bf16``, scale1 / shift1 [nb*64] folded BN, b2 [sum_c] -> NCHW f32 [B,sum_c,H,W]."""
+    """bf16-MFMA version of ``centerhead_branches``: x NHWC f32 or bf16 [B,H,W,ld] (channels [x_coff, x_coff+64); ld and x_coff
+    multiples of 4, of 8 for a bf16 x), ``packed`` from ``pack_centerhead_bf16``, scale1 / shift1 [nb*64] folded BN, b2 [sum_c]
+    -> NCHW f32 [B,sum_c,H,W].  At most HEAD_BF16_MAX_BRANCHES = 48 branches (refused by the C entry) of at most
+    HEAD_BF16_MAX_OUT = 4 outputs each: ``out_begin`` is the table ``pack_centerhead_bf16`` checked -- it is not read back here
+    (no device-to-host sync on the frame path), so pass the same one."""
     B, H, W, ld = (int(s) for s in x.shape)
     assert x.is_contiguous() and x.dtype in (torch.float32, torch.bfloat16)
     total = int(b2.shape[0])
