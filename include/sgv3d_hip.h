@@ -1845,6 +1845,59 @@ int sgv3d_resize_u8_filter(int frames, int in_h, int in_w, int out_h, int out_w,
                            int xksize, const int32_t *ybounds, const int32_t *ycoeffs, int yksize, int swap_rb, const uint8_t *src,
                            uint8_t *tmp, float *dst, void *stream);
 
+/* ---- Detections drawn on the device: box wireframes on the camera frame, rectangles on a BEV canvas, a class-mask overlay
+ * (csrc/render.hip; the contract is DESIGN.md "Rendering detections").  Frames are RGB u8 [batch, height, width, 3]. */
+#define SGV3D_RENDER_MAX_SIDE 8192  /* frame and canvas sides; keeps every product of the coverage rule below 2^62 */
+#define SGV3D_RENDER_MAX_BOXES 1024 /* the largest max_boxes                                                      */
+#define SGV3D_RENDER_GUARD 64       /* segments are clipped to the target grown by this many pixels               */
+#define SGV3D_RENDER_CAM_EDGES 14   /* primitives per box on the camera frame: 12 edges, 2 diagonals of face 0    */
+#define SGV3D_RENDER_BEV_EDGES 4    /* primitives per box on the BEV canvas                                       */
+#define SGV3D_RENDER_EOVERFLOW 1    /* status word: more kept boxes (or labels) than max_boxes; the frame is copied through */
+
+typedef struct {
+    int batch;
+    int n;           /* detection rows per sample (boxes [batch, n, 9]); rows [:counts[b]] are read                 */
+    int m;           /* label rows per sample (label_boxes [batch, m, 7]); 0: no labels                             */
+    int height, width;
+    int bev_h, bev_w;           /* 0, 0: no BEV canvas                                                              */
+    int bev_x_off, bev_y_off;   /* int(floor(side0 / res)) and int(ceil(fwd1 / res)), computed by the caller        */
+    int max_boxes;              /* kept detections and labels are each limited to this many per sample              */
+    int thickness;              /* 1..15; the diagonals of face 0 are always 1                                      */
+    int f64_inputs;             /* 0: boxes and scores are float32, 1: float64                                      */
+    int num_classes;            /* 1..64                                                                            */
+    int mask_alpha;             /* 0..256                                                                           */
+    double score_thr, z_near, bev_res;
+    int8_t class_table[64];     /* class index -> 0, 1, 2 kept, -1 dropped (sgv3d_detections_to_kitti's table)      */
+    uint8_t class_colors[192];  /* RGB per class index                                                              */
+    uint8_t label_color[3], bev_pred_color[3], bev_label_color[3];
+    uint8_t palette[21];        /* RGB per mask class id 0..6 (id 0 is never used)                                  */
+} sgv3d_render_desc;
+
+/* HOST function: workspace bytes of sgv3d_render_detections for this descriptor (0 if the descriptor is invalid). */
+size_t sgv3d_render_workspace_bytes(const sgv3d_render_desc *d);
+
+/* Three launches whatever the batch: setup (keep rule, corners, near-plane cut, projection, clip, integer endpoints in f64),
+ * bin (per 32 x 32 tile a bitmap over primitive numbers), paint (a gather: every pixel takes the colour of the highest-numbered
+ * primitive covering it; no atomics, so a launch is repeatable bit for bit).
+ *   boxes, scores, labels, counts, calib: as sgv3d_detections_to_kitti reads them (calib f64 [batch, 33])
+ *   label_boxes f64 [batch, m, 7] (x, y, z_bottom, ex, ey, h, yaw) with label_counts i32 [batch], or both null with m = 0
+ *   frames u8 [batch, height, width, 3]; masks u8 [batch, height, width] (class id * 40) or null
+ *   out    u8 like frames; out == frames draws in place and leaves tiles without primitives and mask untouched; any other
+ *          overlap is refused
+ *   bev    u8 [batch, bev_h, bev_w, 3], written whole (zeros where nothing is drawn), or null with bev_h = bev_w = 0
+ *   status i32 [batch]: 0 or SGV3D_RENDER_EOVERFLOW
+ * Nothing waits for the host; the call can be captured in a graph. */
+int sgv3d_render_detections(const sgv3d_render_desc *d, const void *boxes, const void *scores, const int32_t *labels,
+                            const int32_t *counts, const double *calib, const double *label_boxes, const int32_t *label_counts,
+                            const uint8_t *frames, const uint8_t *masks, uint8_t *out, uint8_t *bev, int32_t *status,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
+/* HOST function: the same over host pointers through the same geometry and coverage functions (CPU tests, sanitizer builds). */
+int sgv3d_render_detections_host(const sgv3d_render_desc *d, const void *boxes, const void *scores, const int32_t *labels,
+                                 const int32_t *counts, const double *calib, const double *label_boxes,
+                                 const int32_t *label_counts, const uint8_t *frames, const uint8_t *masks, uint8_t *out,
+                                 uint8_t *bev, int32_t *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,15 @@ class SamAttnDesc(ctypes.Structure):
     _fields_ = [(n, c_int) for n in ("batch", "nq", "nk", "heads", "head_dim", "q_ld", "k_ld", "v_ld", "o_ld")] + [("scale", ctypes.c_float)]
 
 
+class RenderDesc(ctypes.Structure):
+    """Mirror of ``sgv3d_render_desc`` (include/sgv3d_hip.h)."""
+    _fields_ = [(n, c_int) for n in ("batch", "n", "m", "height", "width", "bev_h", "bev_w", "bev_x_off", "bev_y_off", "max_boxes",
+                                     "thickness", "f64_inputs", "num_classes", "mask_alpha")] + \
+               [(n, ctypes.c_double) for n in ("score_thr", "z_near", "bev_res")] + \
+               [("class_table", ctypes.c_int8 * 64), ("class_colors", ctypes.c_uint8 * 192), ("label_color", ctypes.c_uint8 * 3),
+                ("bev_pred_color", ctypes.c_uint8 * 3), ("bev_label_color", ctypes.c_uint8 * 3), ("palette", ctypes.c_uint8 * 21)]
+
+
 CONV_NORMAL, CONV_DECONV, CONV_NCHW_OUT, CONV_GROUP_PLANES = 0, 1, 2, 3
 TILE_AUTO, TILE_128x128, TILE_128x64, TILE_64x128, TILE_64x64 = 0, 1, 2, 3, 4
 
@@ -268,6 +277,9 @@ _PROTOS = {
                                   [c_void_p, c_size_t] + [c_void_p] * 4),
     "sgv3d_detections_to_kitti_host": (c_int, [c_int] * 2 + [c_void_p] * 2 + [c_int] + [c_void_p] * 4 + [c_int, ctypes.c_double] +
                                        [c_int] * 4 + [c_void_p] * 3),
+    "sgv3d_render_workspace_bytes": (c_size_t, [ctypes.POINTER(RenderDesc)]),
+    "sgv3d_render_detections": (c_int, [ctypes.POINTER(RenderDesc)] + [c_void_p] * 13 + [c_size_t, c_void_p]),
+    "sgv3d_render_detections_host": (c_int, [ctypes.POINTER(RenderDesc)] + [c_void_p] * 12),
     "sgv3d_recombine_workspace_bytes": (c_size_t, [c_int] * 4),
     "sgv3d_recombine_frames": (c_int, [c_int] * 6 + [c_void_p] * 7 + [c_size_t] + [c_void_p] * 9),
     "sgv3d_recombine_host": (c_int, [c_int] * 6 + [c_void_p] * 14),

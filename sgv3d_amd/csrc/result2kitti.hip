@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "common.hpp"
+#include "kitti_geom.hpp"
 #include "round_decimals.hpp"
 
 namespace {
@@ -25,32 +26,8 @@ using sgv3d::round4;
 
 constexpr int kThreads = 256;                  // four waves per sample
 constexpr int kWaves = kThreads / sgv3d::kWave;
-constexpr int kMaxClasses = 64;
 constexpr int kFields = 13;
 constexpr int kCalib = 33;                     // Tr_velo_to_cam 3x4 | camera matrix 3x3 | ego2global rotation 3x3 | translation 3
-
-struct KittiParams {
-    int n, max_det, digits, num_classes;
-    double thr, img_w, img_h;
-    signed char cls[kMaxClasses];              // class index -> 0 Car, 1 Pedestrian, 2 Cyclist, -1 unmapped
-};
-
-__host__ __device__ inline double dot3(const double *m, double a, double b, double c) {
-    return (m[0] * a + m[1] * b) + m[2] * c;
-}
-
-// Corner k of _box_corners((ex, ey, h), yaw, (x, y, z)) in the lidar frame: the offsets (+-ex/2, +-ey/2, 0 | h) turned by
-// the yaw matrix [[c, -s, 0], [s, c, 0], [0, 0, 1]], plus the bottom centre.
-__host__ __device__ inline void box_corner(int k, double ex, double ey, double h, double c, double s, double x, double y, double z,
-                                           double *p) {
-    const double hx = ex / 2, hy = ey / 2;
-    const double lx = (k & 2) ? -hx : hx;                       // + + - - + + - -
-    const double ly = ((k + 1) & 2) ? -hy : hy;                 // + - - + + - - +
-    const double lz = (k & 4) ? h : 0.0;
-    p[0] = (c * lx + (-s) * ly) + x;
-    p[1] = (s * lx + c * ly) + y;
-    p[2] = lz + z;
-}
 
 // One detection -> the 13 unrounded columns alpha, x1, y1, x2, y2, h, l, w, x, y, z, rotation_y, score.
 template <typename T>
@@ -111,12 +88,6 @@ __host__ __device__ inline void kitti_row(const T *box, T score_f, const double 
     out[10] = (dot3(Tr + 8, x, y, z)) + Tr[11] * 1.0;
     out[11] = 0.5 * pi - yaw;
     out[12] = (double)score_f;
-}
-
-__host__ __device__ inline bool kitti_keep(double score, int label, const KittiParams &P, int *cls) {
-    if (!(score > P.thr) || label < 0 || label >= P.num_classes) return false;
-    *cls = P.cls[label];
-    return *cls >= 0;
 }
 
 template <typename T>
